@@ -14,7 +14,14 @@ without a cloud account; this measures the GPU half on real hardware:
   hand-written, timed interleaved; ``per_rank_k1_variant``; ``--k1-variant NAME``
   times one build), then W untimed warmup steps, then EXACTLY K
   steps bracketed by barrier + synchronize and timed with HIP events, max over
-  ranks; ``value`` = aggregate TFLOP/s over all GPUs,
+  ranks; ``value`` = aggregate TFLOP/s over all GPUs; ``ms_per_step`` = the
+  milliseconds one timed step took,
+* ``--dump-outputs DIR``: right after the timed steps each rank writes the C
+  its last timed step computed to ``DIR/c_rank<r>.npy`` (float32; above
+  DUMP_MAX_BYTES a fixed seeded sample). Operands come from fixed seeds, so
+  two builds run with the same arguments can be compared element for element,
+* a plain run stops there and prints the line (``verified`` null). Everything
+  below runs only with ``--full``,
 * after the timed region (never inside it): full-matrix verification against
   an independent fp32 reference, K1 vs hipBLASLt on the same data measured
   INTERLEAVED (ABAB rounds, median of each), K2 HBM
@@ -28,6 +35,7 @@ without a cloud account; this measures the GPU half on real hardware:
   the phase.
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192]
+                        [--full] [--dump-outputs DIR]
 For N > 1 the driver launches it under ``torch.distributed.run``; launched
 directly with --gpus N > 1 it starts that launcher as a child process.
 """
@@ -80,6 +88,17 @@ def parse(argv=None):
                     help="the K1 build of the timed loop: auto = the faster of the 8-wave plan "
                          "and the 4-wave dma4k_d3 on this box (select_k1); or a build name "
                          "(default, dma4k_d3) to time that one")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything that is not the headline "
+                         "figure: AMD SMI power windows, the stamped-clock and MFMA clock "
+                         "probes, node topology, full-matrix verification, the stream-K check, "
+                         "K1 vs hipBLASLt with energy per flop, ABFT, the HBM check, the "
+                         "collective sweeps (N > 1) and the Job binary. Without it the run sets "
+                         "up, warms up, times the K steps and prints the line (verified = null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (each "
+                         "rank's C, as float32; a fixed seeded sample of it above "
+                         "DUMP_MAX_BYTES) to DIR/c_rank<r>.npy")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     ap.add_argument("--extras-timeout-s", type=float, default=300.0,
                     help="deadline for the work after the timed region (verification, "
@@ -334,6 +353,42 @@ def select_k1(wl, backend, dev, sync, rounds: int = 9, launches: int = 20) -> di
             "rounds": rounds, "launches_per_round": launches}
 
 
+# --dump-outputs writes at most this many bytes, all ranks together
+DUMP_MAX_BYTES = 32 << 20
+DUMP_SEED = 20250117
+
+
+def dump_indices(numel: int, max_elems: int):
+    """Which flat elements --dump-outputs keeps of an output of ``numel``
+    elements: None (all of them) up to ``max_elems``, else ``max_elems`` sorted
+    indices drawn with a fixed seed, the same in every run and every build."""
+    import numpy as np
+
+    if numel <= max_elems:
+        return None
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.integers(0, numel, size=max_elems, dtype=np.int64))
+
+
+def dump_outputs(dirname: str, rank: int, n_ranks: int, c) -> dict:
+    """Write this rank's C (what the last timed step left) as float32 to
+    ``dirname/c_rank<rank>.npy``: the whole [M, N] matrix, or its
+    ``dump_indices`` sample as a 1-D array."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_indices(c.numel(), DUMP_MAX_BYTES // 4 // n_ranks)
+    if idx is None:
+        arr = c.float().cpu().numpy()
+    else:
+        arr = c.reshape(-1)[torch.from_numpy(idx).to(c.device)].float().cpu().numpy()
+    path = os.path.join(dirname, f"c_rank{rank}.npy")
+    np.save(path, arr)
+    return {"file": path, "shape": list(arr.shape), "dtype": str(arr.dtype),
+            "sampled": idx is not None, "of_elements": c.numel()}
+
+
 def node_topology(env, dev) -> dict:
     """What the run ran on, for reading a scaling curve: every rank's device
     (name, PCI bus id, UUID, CUs, HBM), the peer-access matrix over the
@@ -498,7 +553,9 @@ def main(argv=None) -> int:
 
     _ = torch.empty(1, device=dev)
     _CLOCK.mark("hip_init")
-    if dev.type == "cuda":
+    # AMD SMI telemetry (power / throttle windows) is read only with --full
+    telemetry = args.full and dev.type == "cuda"
+    if telemetry:
         smi_sample()   # AMD SMI initialises here, not next to the timed loop
 
     wl = GemmWorkload(args.size, dev, seed=20250117 + env.rank, backend=backend)
@@ -531,7 +588,7 @@ def main(argv=None) -> int:
         for _ in range(POWER_WINDOW_CHUNK):
             wl.step()
         prewarm["launches"] += POWER_WINDOW_CHUNK
-    smi_before = smi_sample() if dev.type == "cuda" else None
+    smi_before = smi_sample() if telemetry else None
     for _ in range(args.warmup):
         wl.step()
     sync()
@@ -548,13 +605,17 @@ def main(argv=None) -> int:
     tmr.stop()
     sync()
     t1 = time.perf_counter()
-    smi_after = smi_sample() if dev.type == "cuda" else None
+    smi_after = smi_sample() if telemetry else None
     dist.barrier(env)
     my_seconds = tmr.seconds()
     elapsed = dist.all_reduce_max(env, my_seconds)
     wall_elapsed = dist.all_reduce_max(env, t1 - t0)
     ms_per_step = elapsed / args.steps * 1e3
     total_tflops = n * wl.flops * args.steps / elapsed / 1e12
+    # ---- what the last timed step computed, before anything else writes C
+    dumped = None
+    if args.dump_outputs:
+        dumped = dist.all_gather_obj(env, dump_outputs(args.dump_outputs, env.rank, n, wl.c))
     # per-rank view (weak-scaling diagnosis; `value` stays the max-over-ranks
     # figure), right after the timed loop, in the power / thermal state it left:
     # each rank's own TF/s, the clock K1 ITSELF runs at (the shipping pingpong8o
@@ -564,7 +625,7 @@ def main(argv=None) -> int:
     # A failure is recorded, never raised: every rank must reach the gather.
     def _probe(name, *a, **kw):
         fn = getattr(backend, name, None)
-        if dev.type != "cuda" or fn is None:
+        if not args.full or dev.type != "cuda" or fn is None:
             return None
         try:
             return fn(*a, **kw)
@@ -581,7 +642,7 @@ def main(argv=None) -> int:
     # by more than 3 % (max / min) is stamped again, up to 3 batches
     # (kernels.gemm_clock_stable; the JSON says how many it took).
     power_steady = None
-    if dev.type == "cuda":
+    if telemetry:
         prewarm_settle(wl.step, sync, 0.3)
         # The firmware metrics behind AMD SMI refresh every few tens of ms, so a
         # short timed loop (20 x 0.67 ms) gets the same counters at both ends. This
@@ -649,9 +710,18 @@ def main(argv=None) -> int:
                 with open(args.out, "w") as f:
                     f.write(s + "\n")
 
+    extras: dict = {}
+    if dumped is not None:
+        extras["dumped_outputs"] = dumped
+    if not args.full:
+        # a plain run ends here: the line holds the headline figure (verified null)
+        _CLOCK.mark("done")
+        emit(make_line(extras, None))
+        dist.shutdown(env)
+        return 0
+
     # ---- after the timed region: verification + context measurements, under a
     # deadline (ExtrasWatchdog): a hung collective must not swallow the JSON line
-    extras: dict = {}
     verified = None
 
     def on_deadline(phase: str) -> int:
@@ -860,6 +930,7 @@ def _make_line_factory(args, n, prewarm, wall_elapsed, ms_per_step, total_tflops
                 "baseline_config": BASELINE_CONFIG,
             },
             "verified": verified,
+            "full": args.full,
             "timing": "HIP events around the K launches (max over ranks); host clock "
                       "around the barrier+sync-bracketed region in timed_region_wall_s",
             "timed_region_wall_s": round(wall_elapsed, 6),
@@ -870,7 +941,8 @@ def _make_line_factory(args, n, prewarm, wall_elapsed, ms_per_step, total_tflops
             "time_to_gpu_ready_in_node_s": (
                 round(extras["validation_job"]["process_start_to_verdict_s"], 3)
                 if (extras.get("validation_job") or {}).get("passed") else None),
-            "bench_process_to_verified_s": round(_CLOCK.elapsed("gemm_verified"), 3),
+            "bench_process_to_verified_s": (round(_CLOCK.elapsed("gemm_verified"), 3)
+                                            if "gemm_verified" in _CLOCK.stamps else None),
             "in_node_phases_s": {k: round(v, 4) for k, v in _CLOCK.durations().items()},
             "per_rank_tflops": [p["tflops"] for p in per_rank],
             # the hand-written K1 build each rank's timed loop ran (select_k1: the

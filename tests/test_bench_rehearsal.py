@@ -44,7 +44,8 @@ def test_torchrun_launch_one_json_line(nproc):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={nproc}", "--master-addr=127.0.0.1", f"--master-port={_port()}",
            str(ROOT / "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-           "--size", "256", "--allreduce-max-mib", "1", "--rehearsal", "--p2p", "--prewarm-s", "0.2"]
+           "--size", "256", "--allreduce-max-mib", "1", "--rehearsal", "--p2p", "--prewarm-s", "0.2",
+           "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
@@ -136,7 +137,7 @@ def test_hung_collective_still_prints_the_line(phase):
            "--master-addr=127.0.0.1", f"--master-port={_port()}", str(ROOT / "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "256",
            "--allreduce-max-mib", "1", "--rehearsal", "--prewarm-s", "0.1",
-           "--extras-timeout-s", "25"]
+           "--extras-timeout-s", "25", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
@@ -235,7 +236,7 @@ def test_bench_on_one_gpu_json_contract(tmp_path):
     verified GEMM, hipBLASLt comparison, HBM check and the Job binary's verdict time."""
     out = tmp_path / "b.json"
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "5", "--warmup", "2",
-                        "--size", "2048", "--out", str(out)],
+                        "--size", "2048", "--out", str(out), "--full"],
                        capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)
@@ -293,6 +294,106 @@ def test_bench_on_one_gpu_json_contract(tmp_path):
     assert job["ran"] and job["passed"], job
     assert 0 < d["time_to_gpu_ready_in_node_s"] < 30
     assert json.loads(out.read_text()) == d
+
+
+# what only a --full run measures: a plain run's line has none of these
+FULL_ONLY_KEYS = {"node_topology", "verify_rank0", "sk_check_rank0", "interleaved_compare_rank0",
+                  "energy_rank0", "abft_rank0", "hbm_copy_GBps_rank0", "validation_job",
+                  "allreduce_bf16", "xgmi_tune"}
+
+
+def _plain_run(extra, timeout=300):
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *extra]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=_env(), cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = _json_lines(p.stdout)
+    assert len(lines) == 1, p.stdout[-2000:]
+    return lines[0]
+
+
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the run times its K steps and prints the line: nothing is
+    verified or compared. --dump-outputs writes the C of the last timed step as
+    float32, identical from run to run (seeded operands)."""
+    import numpy as np
+    import torch
+
+    from nvidia_terraform_modules_amd.ops import reference
+
+    args = ["--steps", "4", "--warmup", "1", "--size", "256", "--rehearsal", "--prewarm-s", "0.05"]
+    runs = []
+    for name in ("a", "b"):
+        d = _plain_run([*args, "--dump-outputs", str(tmp_path / name)])
+        assert CONTRACT_KEYS <= set(d) and d["full"] is False and d["verified"] is None
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "bf16"
+        assert d["unit"] == "TFLOP/s" and d["higher_is_better"] is True
+        assert not FULL_ONLY_KEYS & set(d), FULL_ONLY_KEYS & set(d)
+        (rec,) = d["dumped_outputs"]
+        assert rec["sampled"] is False and rec["shape"] == [256, 256]
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["c_rank0.npy"]
+        runs.append(np.load(tmp_path / name / "c_rank0.npy"))
+    assert runs[0].dtype == np.float32 and runs[0].shape == (256, 256)
+    assert np.array_equal(runs[0], runs[1])
+    # it is the product of the seeded operands (rank 0's seed), as bf16
+    a = reference.fill_uniform_(torch.empty(256, 256, dtype=torch.bfloat16), 20250117 * 2 + 1)
+    b = reference.fill_uniform_(torch.empty(256, 256, dtype=torch.bfloat16), 20250117 * 2 + 2)
+    assert np.array_equal(runs[0], reference.gemm_bf16(a, b).float().numpy())
+
+
+def test_dump_outputs_samples_a_large_output_with_a_fixed_seed(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    assert bench.DUMP_MAX_BYTES <= 64 << 20
+    assert bench.dump_indices(1000, 1000) is None
+    idx = bench.dump_indices(8192 * 8192, 1 << 16)
+    assert idx.shape == (1 << 16,) and np.array_equal(idx, bench.dump_indices(8192 * 8192, 1 << 16))
+    assert np.all(np.diff(idx) >= 0) and 0 <= idx[0] and idx[-1] < 8192 * 8192
+    # every 256 x 256 tile of an 8192^2 output is sampled at the real sample size
+    full = bench.dump_indices(8192 * 8192, bench.DUMP_MAX_BYTES // 4)
+    tiles = np.unique((full // 8192 // 256) * 32 + (full % 8192) // 256)
+    assert len(tiles) == 32 * 32
+    # two ranks share the byte budget; a sampled dump is 1-D float32 of those elements
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 2 * 500)
+    c = torch.arange(64 * 64, dtype=torch.float32).reshape(64, 64).to(torch.bfloat16)
+    rec = bench.dump_outputs(str(tmp_path), 1, 2, c)
+    arr = np.load(tmp_path / "c_rank1.npy")
+    assert rec["sampled"] is True and rec["of_elements"] == 4096 and rec["shape"] == [500]
+    assert arr.dtype == np.float32 and arr.shape == (500,)
+    assert np.array_equal(arr, c.reshape(-1).float().numpy()[bench.dump_indices(4096, 500)])
+
+
+@pytest.mark.gpu
+def test_plain_bench_on_one_gpu_dumps_the_timed_gemm(tmp_path):
+    """The plain run on one MI355X: the headline fields, none of the --full
+    measurements, and the dumped C is the GEMM of the seeded operands (checked
+    here against the independent fp32 reference kernel)."""
+    import numpy as np
+    import torch
+
+    from nvidia_terraform_modules_amd import ops
+    from nvidia_terraform_modules_amd.models.validation_job import GemmWorkload
+
+    d = _plain_run(["--steps", "7", "--warmup", "2", "--size", "2048",
+                    "--dump-outputs", str(tmp_path)])
+    assert CONTRACT_KEYS <= set(d) and d["full"] is False and d["verified"] is None
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["value"] > 50 and "rehearsal" not in d
+    assert d["value"] == pytest.approx(2 * 2048 ** 3 / (d["ms_per_step"] * 1e-3) / 1e12, rel=1e-2)
+    assert not FULL_ONLY_KEYS & set(d), FULL_ONLY_KEYS & set(d)
+    assert d["per_rank_k1_variant"][0] in ("default", "dma4k_d3")
+    assert d["per_rank_power"] == [None] and d["per_rank_gemm_clock"] == [None]
+    c = np.load(tmp_path / "c_rank0.npy")
+    assert c.dtype == np.float32 and c.shape == (2048, 2048)
+    wl = GemmWorkload(2048, torch.device("cuda:0"), seed=20250117)
+    atol, rtol = ops.gemm_tolerance(2048)
+    rep = ops.verify_bf16(torch.from_numpy(c).to("cuda:0").to(torch.bfloat16),
+                          ops.ref_gemm_f32(wl.a, wl.b), atol, rtol)
+    assert rep.ok and rep.bad == 0, rep.as_dict()
 
 
 def test_pair_busbw_pairs_xgmi_with_rccl_sizes():
@@ -418,7 +519,8 @@ def test_bench_two_ranks_on_one_gpu_real_kernels(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", str(ROOT / "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "2048",
-           "--allreduce-max-mib", "16", "--shared-gpu", "--no-job", "--compare-rounds", "3"]
+           "--allreduce-max-mib", "16", "--shared-gpu", "--no-job", "--compare-rounds", "3",
+           "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = _json_lines(p.stdout)

@@ -10,8 +10,8 @@
 #   tests:<k>  pytest -m gpu -k <k>
 #   smoke      __graft_entry__.smoke()
 #   validate   amdgpu-validate on 1 GPU (JSON report)
-#   bench      bench.py exactly as the driver runs it (--steps 20 --warmup 5)
-#   bench200   bench.py --steps 200 --warmup 20
+#   bench      bench.py --full --steps 20 --warmup 5 (headline + every check after it)
+#   bench200   bench.py --full --steps 200 --warmup 20
 #   prof       rocprofv3 --kernel-trace --stats of a short bench
 #   pmc        PMC passes (counters in their own runs, --kernel-trace only) of K1 vs
 #              hipBLASLt at 8192^3 (PMC_DTYPE=fp8: K1-fp8 vs hipBLASLt fp8; PMC_ARGS: extra
@@ -59,16 +59,16 @@ for s in "${STEPS[@]}"; do
         --out "$O/validate_1gpu.json" > "$O/validate.log" 2>&1 || fail validate $? "$O/validate.log"
       tail -3 "$O/validate.log" ;;
     bench)
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --out "$O/bench.json" \
+      timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full --out "$O/bench.json" \
         > "$O/bench.log" 2>&1 || fail bench $? "$O/bench.log"
       tail -c 1500 "$O/bench.json" ;;
     bench200)
-      timeout -k 10 300 python -u bench.py --gpus 1 --steps 200 --warmup 20 --out "$O/bench200.json" \
+      timeout -k 10 300 python -u bench.py --gpus 1 --steps 200 --warmup 20 --full --out "$O/bench200.json" \
         > "$O/bench200.log" 2>&1 || fail bench200 $? "$O/bench200.log"
       tail -c 600 "$O/bench200.json" ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run \
-        -- python3 bench.py --steps 50 --warmup 5 --no-job > "$O/bench_prof.log" 2>&1 \
+        -- python3 bench.py --steps 50 --warmup 5 --full --no-job > "$O/bench_prof.log" 2>&1 \
         || fail prof $? "$O/bench_prof.log"
       find "$O/prof" -name '*kernel_stats.csv' -exec head -12 {} \; ;;
     pmc)
