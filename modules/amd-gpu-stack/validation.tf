@@ -34,6 +34,10 @@ locals {
     var.validation_p2p_floor_gbps > 0 ? [
       "--p2p-floor-gbps", tostring(var.validation_p2p_floor_gbps),
     ] : [],
+    # K4: the full-capacity HBM pattern test, off unless asked for
+    var.validation_hbm_test_gb != 0 ? [
+      "--hbm-test-gb", tostring(var.validation_hbm_test_gb),
+    ] : [],
     local.validation_multi_gpu && var.validation_rccl_busbw_floor_gbps > 0 ? [
       "--rccl-busbw-floor-gbps", tostring(var.validation_rccl_busbw_floor_gbps),
     ] : [],

@@ -301,6 +301,17 @@ variable "validation_min_hbm_gb" {
   description = "Per-GPU HBM capacity floor in GB (MI355X: 288 GB HBM3E)."
 }
 
+variable "validation_hbm_test_gb" {
+  type        = number
+  default     = 0
+  description = "GB (1e9 bytes) of each GPU's HBM that the Job's pattern test (K4) writes, reads back and compares: an address pattern with an in-place inversion, then a hash pattern. 0 turns the test off; -1 tests all free HBM minus a headroom of max(2 GiB, 2 %). Measured cost of -1 on one MI355X (a 1-GPU Job, 302 GB tested): 8-11 s more Job wall time, nearly all of it allocating and releasing the memory; the streaming passes take 0.27 s (profiles/hbm_memtest/README.md). The cost with 8 GPUs allocating at once is unmeasured."
+
+  validation {
+    condition     = var.validation_hbm_test_gb >= -1
+    error_message = "validation_hbm_test_gb must be >= -1 (-1 = all free HBM minus the headroom, 0 = off)."
+  }
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

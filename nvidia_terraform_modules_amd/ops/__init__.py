@@ -8,6 +8,8 @@ K1 ``gemm_bf16``      - 256x256x64 LDS-DMA + MFMA bf16 GEMM (the headline; small
    ``gemm_fp8``         - the same kernels on OCP e4m3 operands (f8f6f4 MFMA; 256x256
                           and the wave-specialised tiles, ``k1_fp8_plan``).
 K2 ``stream_copy``, ``stream_read`` - tuned float4 HBM streams.
+K4 ``hbm_pattern_write``, ``hbm_pattern_verify`` - address / hash pattern fill and
+   on-device compare for the full-capacity HBM test.
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -52,5 +54,10 @@ from .kernels import (  # noqa: F401
     sk_check_enabled,
     stream_copy,
     stream_read,
+    HBM_PATTERN_ADDR,
+    HBM_PATTERN_HASH,
+    HbmPatternReport,
+    hbm_pattern_verify,
+    hbm_pattern_write,
     verify_bf16,
 )

@@ -95,6 +95,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "ntm_stream_read": ([c_vp, c_size, c_vp, c_vp], c_int),
         "ntm_stream_copy_ex": ([c_vp, c_vp, c_size, c_int, c_int, c_int, c_vp], c_int),
         "ntm_stream_read_ex": ([c_vp, c_size, c_vp, c_int, c_int, c_int, c_vp], c_int),
+        "ntm_hbm_pattern_write": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
+                                   c_vp], c_int),
+        "ntm_hbm_pattern_verify": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
+                                    c_int, c_vp, c_vp], c_int),
+        "ntm_hbm_pattern_result_bytes": ([], c_int),
     }
     for name, (argt, rest) in sig.items():
         fn = getattr(lib, name)

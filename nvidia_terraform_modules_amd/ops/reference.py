@@ -12,9 +12,11 @@ the device hash RNG: rehearsal numbers are not comparable to device ones).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
-from .kernels import AbftReport, VerifyReport, gemm_shape_ok, gemm_tolerance  # noqa: F401
+from .kernels import (AbftReport, HbmPatternReport, VerifyReport, gemm_shape_ok,  # noqa: F401
+                      gemm_tolerance, hbm_pattern_check_args, hbm_pattern_id)
 
 
 def fill_uniform_(t: torch.Tensor, seed: int, scale: float = 1.0) -> torch.Tensor:
@@ -74,3 +76,56 @@ def stream_read(src, sink, config="tuned") -> None:
     s = float(src.float().sum())
     if s != s:
         sink[0] = s
+
+
+# K4 on the CPU, written from the pattern's definition (validation/README.md), with
+# w = (base + byte offset) / 4 the 64-bit global index of a 32-bit word:
+#   ADDR: each 8-byte word = (w / 2) ^ seed;  HASH: each 32-bit word = x ^ hi(w) * 0x9E3779B9
+#   with x = lo(w) + (uint32)seed; x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15.
+def hbm_pattern_words(nbytes: int, pattern, seed: int = 0, invert: bool = False,
+                      base: int = 0) -> np.ndarray:
+    """The pattern of logical bytes ``base .. base + nbytes`` as little-endian uint32 words."""
+    pat = hbm_pattern_id(pattern)
+    seed &= 2**64 - 1
+    if pat == 0:
+        q = np.arange(nbytes // 8, dtype=np.uint64) + np.uint64(base // 8)
+        words = (q ^ np.uint64(seed)).view(np.uint32)
+    else:
+        w = np.arange(nbytes // 4, dtype=np.uint64) + np.uint64(base // 4)
+        x = (w + np.uint64(seed & 0xFFFFFFFF)).astype(np.uint32)
+        x ^= x >> np.uint32(16)
+        x *= np.uint32(0x7FEB352D)
+        x ^= x >> np.uint32(15)
+        words = x ^ ((w >> np.uint64(32)).astype(np.uint32) * np.uint32(0x9E3779B9))
+    return ~words if invert else words
+
+
+def _bytes_of(t: torch.Tensor) -> np.ndarray:
+    if t.is_cuda:
+        raise ValueError("ops.reference works on CPU tensors")
+    return t.view(-1).view(torch.uint8).numpy()
+
+
+def hbm_pattern_write(t: torch.Tensor, pattern, seed: int = 0, invert: bool = False,
+                      base: int = 0) -> torch.Tensor:
+    nbytes = hbm_pattern_check_args(t, base)
+    _bytes_of(t)[:] = hbm_pattern_words(nbytes, pattern, seed, invert, base).view(np.uint8)
+    return t
+
+
+def hbm_pattern_verify(t: torch.Tensor, pattern, seed: int = 0, invert: bool = False,
+                       base: int = 0, invert_after: bool = False) -> HbmPatternReport:
+    nbytes = hbm_pattern_check_args(t, base)
+    exp = hbm_pattern_words(nbytes, pattern, seed, invert, base)
+    mem = _bytes_of(t)
+    e64, g64 = exp.view(np.uint64), mem.view(np.uint64).copy()
+    if invert_after:
+        mem[:] = (~exp).view(np.uint8)
+    diff = e64 ^ g64
+    idx = np.flatnonzero(diff)
+    recs = [{"offset": base + 8 * int(i), "expected": int(e64[i]), "got": int(g64[i])}
+            for i in idx[:4]]
+    return HbmPatternReport(
+        bad_words=int(idx.size),
+        bad_bits=int(np.bitwise_or.reduce(diff[idx])) if idx.size else 0,
+        first_bad_offset=base + 8 * int(idx[0]) if idx.size else None, records=recs)

@@ -1,5 +1,5 @@
 // C ABI over the MI355X validation kernels (K1 GEMM, K2 HBM stream,
-// K3 fill/reference/verify). Built for gfx950 only into
+// K3 fill/reference/verify, K4 HBM pattern test). Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
 // Every entry point is stream-ordered, allocation-free and sync-free, so it
@@ -20,6 +20,7 @@
 #include "ntm/gemm_bf16_t128.hpp"
 #include "ntm/gemm_fp8.hpp"
 #include "ntm/gemm_w4k.hpp"
+#include "ntm/hbm_pattern.hpp"
 
 #define NTM_API extern "C" __attribute__((visibility("default")))
 
@@ -1187,4 +1188,68 @@ NTM_API int ntm_stream_copy(const void* src, void* dst, size_t bytes,
 NTM_API int ntm_stream_read(const void* src, size_t bytes, float* sink,
                             void* stream) {
   return ntm_stream_read_ex(src, bytes, sink, 8, 1, 1024, stream);
+}
+
+// K4: HBM pattern test (hbm_pattern.hpp). One block per tile (4 KiB for the
+// write, 8 KiB like the tuned K2 copy for the verify kernels). `result` is one ntm::hbm::PatternResult the caller has
+// initialised (zero, first_bad_offset all ones); the kernels only add to it, so
+// one record can collect a whole step. Offsets in it are logical: base_bytes +
+// the offset in this buffer. invert_after: store the complement of the expected
+// pattern behind the compare (moving inversions).
+namespace {
+template <int PAT>
+void pattern_write_p(void* ptr, size_t n4, uint64_t base_w, uint64_t seed, uint32_t inv,
+                     hipStream_t s) {
+  using namespace ntm::hbm;
+  const unsigned g = tiled_grid(n4, kWriteUnroll, 0);
+  hipLaunchKernelGGL((hbm_pattern_write_kernel<PAT, kWriteUnroll>), dim3(g), dim3(256), 0, s,
+                     (u32x4*)ptr, n4, base_w, seed, inv);
+}
+template <int PAT, bool INV>
+void pattern_verify_p(void* ptr, size_t n4, uint64_t base_w, uint64_t seed, uint32_t inv,
+                      void* result, hipStream_t s) {
+  using namespace ntm::hbm;
+  const unsigned g = tiled_grid(n4, kVerifyUnroll, 0);
+  hipLaunchKernelGGL((hbm_pattern_verify_kernel<PAT, kVerifyUnroll, INV>), dim3(g), dim3(256), 0,
+                     s, (u32x4*)ptr, n4, base_w, seed, inv, (PatternResult*)result);
+}
+bool pattern_args_ok(const void* ptr, size_t bytes, unsigned long long base_bytes, int pattern) {
+  return ptr && (uintptr_t)ptr % 16 == 0 && bytes % 16 == 0 && base_bytes % 16 == 0 &&
+         (pattern == ntm::hbm::kPatternAddr || pattern == ntm::hbm::kPatternHash);
+}
+}  // namespace
+
+NTM_API int ntm_hbm_pattern_result_bytes() { return (int)sizeof(ntm::hbm::PatternResult); }
+
+NTM_API int ntm_hbm_pattern_write(void* ptr, size_t bytes, unsigned long long base_bytes,
+                                  int pattern, unsigned long long seed, int invert,
+                                  void* stream) {
+  if (!pattern_args_ok(ptr, bytes, base_bytes, pattern)) return (int)hipErrorInvalidValue;
+  if (bytes == 0) return 0;
+  const uint32_t inv = invert ? ~0u : 0u;
+  if (pattern == ntm::hbm::kPatternAddr)
+    pattern_write_p<ntm::hbm::kPatternAddr>(ptr, bytes / 16, base_bytes / 4, seed, inv, S(stream));
+  else
+    pattern_write_p<ntm::hbm::kPatternHash>(ptr, bytes / 16, base_bytes / 4, seed, inv, S(stream));
+  return (int)hipGetLastError();
+}
+
+NTM_API int ntm_hbm_pattern_verify(void* ptr, size_t bytes, unsigned long long base_bytes,
+                                   int pattern, unsigned long long seed, int invert,
+                                   int invert_after, void* result, void* stream) {
+  if (!pattern_args_ok(ptr, bytes, base_bytes, pattern) || !result || (uintptr_t)result % 64)
+    return (int)hipErrorInvalidValue;
+  if (bytes == 0) return 0;
+  const uint32_t inv = invert ? ~0u : 0u;
+  const size_t n4 = bytes / 16;
+  const uint64_t bw = base_bytes / 4;
+  using namespace ntm::hbm;
+  if (pattern == kPatternAddr) {
+    if (invert_after) pattern_verify_p<kPatternAddr, true>(ptr, n4, bw, seed, inv, result, S(stream));
+    else pattern_verify_p<kPatternAddr, false>(ptr, n4, bw, seed, inv, result, S(stream));
+  } else {
+    if (invert_after) pattern_verify_p<kPatternHash, true>(ptr, n4, bw, seed, inv, result, S(stream));
+    else pattern_verify_p<kPatternHash, false>(ptr, n4, bw, seed, inv, result, S(stream));
+  }
+  return (int)hipGetLastError();
 }

@@ -7,6 +7,8 @@
 //   K1  hand-written bf16 MFMA GEMM per GPU (TFLOP/s + full verification
 //       against an independent fp32 reference kernel)
 //   K2  HBM stream copy bandwidth + capacity check (288 GB class)
+//   K4  HBM pattern test over (up to) all free HBM, off by default
+//       (--hbm-test-gb; ntm/hbm_pattern.hpp)
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL
@@ -38,6 +40,7 @@
 #include <unistd.h>
 
 #include "ntm/common.hpp"
+#include "ntm/hbm_test_plan.hpp"
 
 namespace ntm {
 namespace xgmi {
@@ -76,6 +79,10 @@ size_t ntm_skh_ws_bytes(int, int, int, int);
 int ntm_gemm_bf16_skh_ex(int, const void*, const void*, void*, int, int, int, int, int, int, void*,
                          size_t, int, void*);
 int ntm_sk_error_word_index();
+int ntm_hbm_pattern_write(void*, size_t, unsigned long long, int, unsigned long long, int, void*);
+int ntm_hbm_pattern_verify(void*, size_t, unsigned long long, int, unsigned long long, int, int,
+                           void*, void*);
+int ntm_hbm_pattern_result_bytes();
 }
 
 namespace {
@@ -110,6 +117,8 @@ struct Opts {
   double tflops_floor = 0;
   double min_hbm_gb = 0;
   double hbm_floor_gbps = 0;
+  double hbm_test_gb = 0;       // K4: 0 = off, < 0 = all free HBM minus the headroom
+  int hbm_test_passes = 1;
   long allreduce_max_mib = 8192;  // 8 GiB, capped by free HBM
   bool xgmi = true;
   int xgmi_sim = 0;             // C2 with N simulated ranks on GPU 0 (one-GPU test path)
@@ -133,7 +142,7 @@ struct Opts {
   std::string out;
   std::string termination_log;  // k8s terminationMessagePath (<= 4 KiB summary)
   std::string prom_out;         // Prometheus textfile-collector metrics
-  std::string fault;            // fault injection: corrupt_gemm | corrupt_abft | corrupt_allreduce
+  std::string fault;            // fault injection: corrupt_gemm | corrupt_abft | corrupt_hbm | ...
   std::string pushgateway;      // http://host[:port][/prefix] of a Prometheus Pushgateway
 };
 
@@ -141,6 +150,7 @@ void usage() {
   std::fprintf(stderr,
                "usage: amdgpu-validate [--gpus N] [--size 8192] [--iters 50]\n"
                "       [--tflops-floor TF] [--min-hbm-gb GB] [--hbm-floor-gbps GBps]\n"
+               "       [--hbm-test-gb GB] [--hbm-test-passes P]\n"
                "       [--allreduce-max-mib MiB] [--rccl | --no-rccl] [--no-xgmi] [--xgmi-sim N]\n"
                "       [--settle-s S] [--no-fp8] [--fp8-tflops-floor TF]\n"
                "       [--no-p2p] [--p2p-mib MiB] [--p2p-floor-gbps GBps] [--p2p-loopback]\n"
@@ -151,9 +161,13 @@ void usage() {
                "       [--termination-log FILE] [--prom-out FILE] [--fault-inject KIND]\n"
                "       [--pushgateway http://host:port]\n"
                "fault-inject (also env NTM_FAULT_INJECT): corrupt_gemm | corrupt_abft |\n"
-               "       corrupt_fp8 | corrupt_fp8_abft | corrupt_p2p | corrupt_allreduce | sk_xcc -\n"
-               "       corrupts the LAST GPU's data (sk_xcc: its stream-K launch claims a wrong\n"
-               "       XCD) to prove detection\n");
+               "       corrupt_fp8 | corrupt_fp8_abft | corrupt_p2p | corrupt_allreduce |\n"
+               "       corrupt_hbm | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
+               "       launch claims a wrong XCD; corrupt_hbm: one bit of the pattern test's\n"
+               "       last chunk, needs --hbm-test-gb) to prove detection\n"
+               "hbm-test-gb: K4, write / read back / compare an address pattern and a hash\n"
+               "       pattern over GB (1e9 bytes) of each GPU's HBM; 0 = off (default), -1 = all\n"
+               "       free HBM minus max(2 GiB, 2 %%); hbm-test-passes: repeat it P times\n");
 }
 
 bool parse(int argc, char** argv, Opts& o) {
@@ -173,6 +187,8 @@ bool parse(int argc, char** argv, Opts& o) {
     else if (a == "--tflops-floor") { if (!(v = next(a.c_str()))) return false; o.tflops_floor = std::atof(v); }
     else if (a == "--min-hbm-gb") { if (!(v = next(a.c_str()))) return false; o.min_hbm_gb = std::atof(v); }
     else if (a == "--hbm-floor-gbps") { if (!(v = next(a.c_str()))) return false; o.hbm_floor_gbps = std::atof(v); }
+    else if (a == "--hbm-test-gb") { if (!(v = next(a.c_str()))) return false; o.hbm_test_gb = std::atof(v); }
+    else if (a == "--hbm-test-passes") { if (!(v = next(a.c_str()))) return false; o.hbm_test_passes = std::atoi(v); }
     else if (a == "--allreduce-max-mib") { if (!(v = next(a.c_str()))) return false; o.allreduce_max_mib = std::atol(v); }
     else if (a == "--no-xgmi") o.xgmi = false;
     else if (a == "--no-rccl") o.rccl = 0;
@@ -203,7 +219,8 @@ bool parse(int argc, char** argv, Opts& o) {
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return false; }
   }
   return o.size > 0 && o.iters > 0 && o.p2p_mib > 0 && o.allreduce_max_mib > 0 &&
-         o.xgmi_sim >= 0 && o.xgmi_sim <= ntm::xgmi::kMaxRanks && o.settle_s >= 0;
+         o.xgmi_sim >= 0 && o.xgmi_sim <= ntm::xgmi::kMaxRanks && o.settle_s >= 0 &&
+         o.hbm_test_passes >= 1 && std::isfinite(o.hbm_test_gb);
 }
 
 // ------------------------------------------------------------ JSON helpers
@@ -295,6 +312,14 @@ struct GpuResult {
   double hbm_copy_gbps = 0, hbm_read_gbps = 0;
   bool hbm_copy_ok = false;
   double t_init = 0, t_gemm = 0, t_hbm = 0;
+  // K4 (only with --hbm-test-gb)
+  bool hbm_test_ran = false;
+  double hbm_test_gb = 0, hbm_test_requested_gb = 0;
+  unsigned long long hbm_test_bad_words = 0, hbm_test_bad_bits = 0;
+  double hbm_test_write_gbps = 0, hbm_test_verify_gbps = 0, hbm_test_s = 0;
+  double hbm_test_alloc_s = 0, hbm_test_free_s = 0;
+  std::string hbm_test_steps;    // JSON array of per-step seconds
+  std::string hbm_test_failure;  // empty = clean
 };
 
 // The split-mode self-check shape: 48 x 5 of 192x256 tiles, half a round on
@@ -350,6 +375,100 @@ bool run_sk_check(int dev, bool last, const Opts& o, hipStream_t s, void* V, Gpu
   CK(hipFree(C));
   CK(hipFree(R));
   CK(hipFree(W));
+  return true;
+}
+
+// ---- K4: HBM pattern test (ntm/hbm_pattern.hpp, plan in ntm/hbm_test_plan.hpp).
+// Allocates the plan's chunks (a failed hipMalloc ends the list), then per pass:
+// write ADDR / verify + invert in place / verify inverted / write HASH (seed =
+// pass) / verify. Every chunk of a step is enqueued back to back; the one error
+// record is read once per step. The first step that finds a bad word ends the test.
+bool run_hbm_test(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r) {
+  namespace hb = ntm::hbm;
+  const auto t_begin = Clock::now();
+  auto since = [](Clock::time_point t0) {
+    return std::chrono::duration<double>(Clock::now() - t0).count();
+  };
+  size_t fre = 0, tot = 0;
+  CK(hipMemGetInfo(&fre, &tot));
+  const hb::TestPlan plan = hb::make_test_plan(fre, o.hbm_test_gb);
+  r.hbm_test_ran = true;
+  r.hbm_test_requested_gb = plan.requested_bytes / 1e9;
+  struct Chunk { void* p; size_t bytes; unsigned long long base; };
+  std::vector<Chunk> chunks;
+  unsigned long long tested = 0;
+  for (uint64_t c : plan.chunks) {
+    void* p = nullptr;
+    if (hipMalloc(&p, c) != hipSuccess) {
+      (void)hipGetLastError();  // out of memory here shortens the test, it is no HIP failure
+      break;
+    }
+    chunks.push_back({p, (size_t)c, tested});
+    tested += c;
+  }
+  r.hbm_test_alloc_s = since(t_begin);
+  r.hbm_test_gb = tested / 1e9;
+  if (chunks.empty()) {
+    if (!plan.chunks.empty()) r.hbm_test_failure = "gpu" + std::to_string(dev) + ": HBM pattern test: no chunk of " + std::to_string(plan.chunks[0]) + " bytes could be allocated";
+    else r.hbm_test_failure = "gpu" + std::to_string(dev) + ": HBM pattern test: no free HBM beyond the headroom";
+    r.hbm_test_s = since(t_begin);
+    return true;
+  }
+  hb::PatternResult* dres;
+  CK(hipMalloc(&dres, sizeof(hb::PatternResult)));
+  hb::PatternResult hres, init;
+  hb::pattern_result_init(init);
+  double t_write = 0, t_verify = 0;
+  unsigned long long b_write = 0, b_verify = 0;
+  std::string steps = "[";
+  bool injected = false;
+  // one step: kind 0 = write, 1 = verify, 2 = verify + invert in place
+  auto step = [&](const char* name, int kind, int pattern, unsigned long long seed, int invert) -> bool {
+    const auto t0 = Clock::now();
+    if (kind) CK(hipMemcpyAsync(dres, &init, sizeof init, hipMemcpyHostToDevice, s));
+    for (auto& c : chunks) {
+      if (kind == 0) CK(ntm_hbm_pattern_write(c.p, c.bytes, c.base, pattern, seed, invert, s));
+      else CK(ntm_hbm_pattern_verify(c.p, c.bytes, c.base, pattern, seed, invert, kind == 2, dres, s));
+    }
+    if (kind) CK(hipMemcpyAsync(&hres, dres, sizeof hres, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    const double dt = since(t0);
+    steps += std::string(steps.size() > 1 ? "," : "") + "{\"step\":" + jstr(name) + ",\"s\":" + jnum(dt) + "}";
+    if (kind == 0) { t_write += dt; b_write += tested; }
+    if (kind == 1) { t_verify += dt; b_verify += tested; }
+    if (kind && hres.bad_words) {
+      r.hbm_test_bad_words = hres.bad_words;
+      r.hbm_test_bad_bits = hres.bad_bits_or;
+      r.hbm_test_failure = hb::failure_message(dev, name, hres);
+    }
+    return true;
+  };
+  for (int pass = 0; pass < o.hbm_test_passes && r.hbm_test_failure.empty(); ++pass) {
+    if (!step("addr write", 0, hb::kPatternAddr, 0, 0)) return false;
+    if (last && o.fault == "corrupt_hbm" && !injected) {  // flip one bit in the last chunk
+      injected = true;
+      const Chunk& c = chunks.back();
+      uint32_t* w = (uint32_t*)((char*)c.p + ((c.bytes / 2) & ~(size_t)15) + 4);
+      uint32_t h;
+      CK(hipMemcpy(&h, w, 4, hipMemcpyDeviceToHost));
+      h ^= 1u << 13;
+      CK(hipMemcpy(w, &h, 4, hipMemcpyHostToDevice));
+    }
+    if (!step("addr verify+invert", 2, hb::kPatternAddr, 0, 0)) return false;
+    if (!r.hbm_test_failure.empty()) break;
+    if (!step("addr inverted verify", 1, hb::kPatternAddr, 0, 1)) return false;
+    if (!r.hbm_test_failure.empty()) break;
+    if (!step("hash write", 0, hb::kPatternHash, (unsigned long long)pass, 0)) return false;
+    if (!step("hash verify", 1, hb::kPatternHash, (unsigned long long)pass, 0)) return false;
+  }
+  r.hbm_test_steps = steps + "]";
+  if (t_write > 0) r.hbm_test_write_gbps = b_write / t_write / 1e9;
+  if (t_verify > 0) r.hbm_test_verify_gbps = b_verify / t_verify / 1e9;
+  const auto t_free = Clock::now();
+  CK(hipFree(dres));
+  for (auto& c : chunks) CK(hipFree(c.p));
+  r.hbm_test_free_s = since(t_free);
+  r.hbm_test_s = since(t_begin);
   return true;
 }
 
@@ -588,6 +707,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   }
   CK(hipFree(src));
   CK(hipFree(dst));
+  if (o.hbm_test_gb != 0 && !run_hbm_test(dev, last, o, s, r)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));
@@ -1279,6 +1399,7 @@ int main(int argc, char** argv) {
     if (o.min_hbm_gb > 0 && r.total_gb < o.min_hbm_gb)
       fail(d + "HBM " + jnum(r.total_gb) + " GB below " + jnum(o.min_hbm_gb) + " GB");
     if (!r.hbm_copy_ok) fail(d + "HBM copy mismatch");
+    if (!r.hbm_test_failure.empty()) fail(r.hbm_test_failure);
     if (o.hbm_floor_gbps > 0 && r.hbm_copy_gbps < o.hbm_floor_gbps)
       fail(d + "HBM copy " + jnum(r.hbm_copy_gbps) + " GB/s below floor");
   }
@@ -1337,6 +1458,18 @@ int main(int argc, char** argv) {
     p << "# TYPE amdgpu_validate_hbm_total_gb gauge\n";
     for (auto& r : res)
       p << "amdgpu_validate_hbm_total_gb{gpu=\"" << r.device << "\"} " << jnum(r.total_gb) << "\n";
+    if (o.hbm_test_gb != 0) {
+      p << "# HELP amdgpu_validate_hbm_test_gb HBM written, read back and compared by the pattern test.\n"
+        << "# TYPE amdgpu_validate_hbm_test_gb gauge\n";
+      for (auto& r : res)
+        if (r.hbm_test_ran)
+          p << "amdgpu_validate_hbm_test_gb{gpu=\"" << r.device << "\"} " << jnum(r.hbm_test_gb) << "\n";
+      p << "# HELP amdgpu_validate_hbm_test_bad_words 8-byte words the pattern test read back wrong.\n"
+        << "# TYPE amdgpu_validate_hbm_test_bad_words gauge\n";
+      for (auto& r : res)
+        if (r.hbm_test_ran)
+          p << "amdgpu_validate_hbm_test_bad_words{gpu=\"" << r.device << "\"} " << r.hbm_test_bad_words << "\n";
+    }
     if (!rccl_rows.empty() || !xgmi_rows.empty())
       p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
         << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(peak_rccl) << "\n"
@@ -1385,7 +1518,19 @@ int main(int argc, char** argv) {
           ",\"sk_xcc_error\":" + std::to_string(r.sk_word) +
           ",\"sk_split_ms\":" + jnum(r.sk_ms) +
           ",\"hbm_copy_GBps\":" + jnum(r.hbm_copy_gbps) +
-          ",\"hbm_read_GBps\":" + jnum(r.hbm_read_gbps) + "}";
+          ",\"hbm_read_GBps\":" + jnum(r.hbm_read_gbps);
+    if (r.hbm_test_ran)
+      js += ",\"hbm_test_gb\":" + jnum(r.hbm_test_gb) +
+            ",\"hbm_test_requested_gb\":" + jnum(r.hbm_test_requested_gb) +
+            ",\"hbm_test_bad_words\":" + std::to_string(r.hbm_test_bad_words) +
+            ",\"hbm_test_bad_bits\":" + std::to_string(r.hbm_test_bad_bits) +
+            ",\"hbm_test_write_GBps\":" + jnum(r.hbm_test_write_gbps) +
+            ",\"hbm_test_verify_GBps\":" + jnum(r.hbm_test_verify_gbps) +
+            ",\"hbm_test_s\":" + jnum(r.hbm_test_s) +
+            ",\"hbm_test_alloc_s\":" + jnum(r.hbm_test_alloc_s) +
+            ",\"hbm_test_free_s\":" + jnum(r.hbm_test_free_s) +
+            ",\"hbm_test_steps\":" + (r.hbm_test_steps.empty() ? std::string("[]") : r.hbm_test_steps);
+    js += "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(rccl_rows);
   js += ",\"xgmi_allreduce_bf16\":" + coll_json(xgmi_rows);
