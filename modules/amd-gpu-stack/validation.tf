@@ -49,6 +49,8 @@ locals {
     local.validation_multi_gpu ? ["--xgmi-tune"] : [],
     var.node_prep_enabled && var.validation_require_host_prep ? ["--require-host-prep"] : [],
     var.validation_require_iommu_pt ? ["--require-iommu-pt"] : [],
+    # K5: the per-CU compute sweep, off unless asked for
+    var.validation_cu_sweep ? ["--cu-sweep"] : [],
     # one-line verdict surfaced as the pod's termination message
     ["--termination-log", "/dev/termination-log"],
   )

@@ -312,6 +312,12 @@ variable "validation_hbm_test_gb" {
   }
 }
 
+variable "validation_cu_sweep" {
+  type        = bool
+  default     = false
+  description = "Run the Job's per-CU compute sweep (K5): known-answer LDS, VALU, bf16 MFMA and fp8 MFMA sub-tests on every compute unit, 4 workgroups per CU and launch until every CU ran one (at most 8 launches). A wrong result fails the Job and names the XCD, SE, SH, CU and SIMD; a CU that ran no workgroup fails it too. Measurements: profiles/cu_sweep/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

@@ -10,6 +10,8 @@ K1 ``gemm_bf16``      - 256x256x64 LDS-DMA + MFMA bf16 GEMM (the headline; small
 K2 ``stream_copy``, ``stream_read`` - tuned float4 HBM streams.
 K4 ``hbm_pattern_write``, ``hbm_pattern_verify`` - address / hash pattern fill and
    on-device compare for the full-capacity HBM test.
+K5 ``cu_sweep``, ``cu_sweep_decode``, ``cu_sweep_summarize`` - known-answer LDS / VALU /
+   MFMA sub-tests per workgroup, tied to the CU that ran them.
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -59,5 +61,11 @@ from .kernels import (  # noqa: F401
     HbmPatternReport,
     hbm_pattern_verify,
     hbm_pattern_write,
+    CU_SWEEP_SUBTESTS,
+    cu_sweep,
+    cu_sweep_decode,
+    cu_sweep_max_lds_bytes,
+    cu_sweep_record_dtype,
+    cu_sweep_summarize,
     verify_bf16,
 )

@@ -100,6 +100,17 @@ def _declare(lib: ctypes.CDLL) -> None:
         "ntm_hbm_pattern_verify": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
                                     c_int, c_vp, c_vp], c_int),
         "ntm_hbm_pattern_result_bytes": ([], c_int),
+        "ntm_cu_sweep_record_bytes": ([], c_int),
+        "ntm_cu_sweep_expected_bytes": ([c_int], c_size),
+        "ntm_cu_sweep_expected": ([c_int, ctypes.c_uint, c_vp, c_size], c_int),
+        "ntm_cu_sweep_lds_words": ([ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_vp],
+                                   c_int),
+        "ntm_cu_sweep_max_lds_bytes": ([c_int], c_int),
+        "ntm_cu_sweep_launch": ([c_vp, c_vp, ctypes.c_uint, c_int, c_size, ctypes.c_uint,
+                                 ctypes.c_uint, c_int, c_vp], c_int),
+        "ntm_cu_sweep_decode": ([ctypes.c_uint, ctypes.c_uint, c_vp], None),
+        "ntm_cu_sweep_summarize": ([c_vp, c_size, ctypes.c_uint, ctypes.c_uint, c_int, c_vp, c_size],
+                                   c_size),
     }
     for name, (argt, rest) in sig.items():
         fn = getattr(lib, name)

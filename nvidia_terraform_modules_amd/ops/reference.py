@@ -129,3 +129,111 @@ def hbm_pattern_verify(t: torch.Tensor, pattern, seed: int = 0, invert: bool = F
         bad_words=int(idx.size),
         bad_bits=int(np.bitwise_or.reduce(diff[idx])) if idx.size else 0,
         first_bad_offset=base + 8 * int(idx[0]) if idx.size else None, records=recs)
+
+
+# K5 on the CPU: the expected tables of the per-CU compute sweep, written from the
+# definitions in validation/include/ntm/cu_sweep_plan.hpp with numpy integer arithmetic
+# (uint32 / uint64 wrap-around, int64 sums). One round = 7680 32-bit words:
+#   hash u32[256] | mad u64[256] | f32 bits[256] | f64 bits[256] |
+#   bf16 16x16 f32 bits [4][16][16] | bf16 32x32 [4][32][32] | fp8 16x16 [4][16][16]
+CU_SWEEP_ROUND_WORDS = 7680
+
+
+def _h32(x: np.ndarray) -> np.ndarray:
+    x = x.astype(np.uint32)
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def _u32(v: int) -> np.ndarray:
+    return np.array([v & 0xFFFFFFFF], dtype=np.uint32)
+
+
+def cu_sweep_round_seed(seed: int, rnd: int) -> int:
+    return int(_h32(_u32(seed + 0x9E3779B9 * (rnd + 1)))[0])
+
+
+def cu_sweep_lds_words(seed: int, rnd: int, nwords: int) -> np.ndarray:
+    """The words the lds sub-test writes in round ``rnd`` (then their complement)."""
+    return _h32(np.arange(nwords, dtype=np.uint32) + np.uint32(cu_sweep_round_seed(seed, rnd)))
+
+
+def cu_sweep_operands(rs: int, kind: int, n: int, k: int, fp8: bool) -> np.ndarray:
+    """[4 waves][n][k] integer operands: row i of A (even kind) or column i of B (odd kind)."""
+    w, i, kk = np.meshgrid(np.arange(4, dtype=np.uint32), np.arange(n, dtype=np.uint32),
+                           np.arange(k, dtype=np.uint32), indexing="ij")
+    idx = ((((np.uint32(kind * 4) + w) * np.uint32(32) + i) << np.uint32(8)) | kk) + np.uint32(rs)
+    h = _h32(idx) >> np.uint32(8)
+    return ((h & np.uint32(7)).astype(np.int64) - 4 if fp8
+            else (h & np.uint32(15)).astype(np.int64) - 8)
+
+
+def _fma_chain(rs: int, chain: int, steps: int, segments: int) -> np.ndarray:
+    t = np.arange(256, dtype=np.uint32)
+    coeff = lambda i: _h32(_u32(rs) + _u32((chain * 64 + i + 1) << 12) + t)  # noqa: E731
+    big = (7, 5) if chain else (3, 2)
+    total = np.zeros(256, dtype=np.int64)
+    for s in range(segments):
+        c0 = coeff(s * steps)
+        acc = ((c0 >> np.uint32(16)) & np.uint32(0xFF)).astype(np.int64) - 128
+        for i in range(steps):
+            c = coeff(s * steps + i)
+            mul = np.where(c & np.uint32(1), big[0], big[1]) * np.where(c & np.uint32(2), -1, 1)
+            acc = acc * mul + (((c >> np.uint32(8)) & np.uint32(0xFF)).astype(np.int64) - 128)
+            assert np.abs(acc).max() < (2**53 if chain else 2**24)
+        total += acc
+    return total
+
+
+def cu_sweep_expected(iters: int, seed: int, lds_bytes: int) -> dict:
+    """Expected values of ``ops.cu_sweep(iters=, seed=, lds_bytes=)``: ``table`` (uint32, the
+    device table, iters * 7680 words), its sections per round (``hash``, ``mad``, ``f32``, ``f64``,
+    ``bf16_16``, ``bf16_32``, ``fp8``), the integer operands (``*_a`` [iters][4][n][K], ``*_b``
+    [iters][4][n][K] by column), ``peak``: the largest sum of |a * b| of any element, which
+    bounds every partial sum whatever the order, and ``lds``: [iters][lds_bytes / 4] fill words."""
+    if not 1 <= iters <= 1024 or lds_bytes < 16 or lds_bytes % 16:
+        raise ValueError("cu_sweep_expected needs 1 <= iters <= 1024 and lds_bytes % 16 == 0")
+    seed &= 0xFFFFFFFF
+    t = np.arange(256, dtype=np.uint32)
+    out = {k: [] for k in ("hash", "mad", "f32", "f64", "bf16_16", "bf16_32", "fp8", "lds",
+                           "bf16_16_a", "bf16_16_b", "bf16_32_a", "bf16_32_b", "fp8_a", "fp8_b")}
+    rows, peak = [], 0
+    for r in range(iters):
+        rs = cu_sweep_round_seed(seed, r)
+        x = t * np.uint32(0x9E3779B9) + np.uint32(rs)
+        for i in range(16):
+            x = _h32(x + np.uint32(i))
+        a = _h32(np.uint32(rs) + np.uint32(2) * t + np.uint32(1))
+        b = _h32(np.uint32(rs) ^ (t * np.uint32(0x85EBCA6B)))
+        acc = a.astype(np.uint64)
+        for i in range(16):
+            acc = a.astype(np.uint64) * b.astype(np.uint64) + acc
+            a = acc.astype(np.uint32) + np.uint32(i)
+            b = (acc >> np.uint64(32)).astype(np.uint32) | np.uint32(1)
+        f32 = _fma_chain(rs, 0, 8, 4).astype(np.float32).view(np.uint32)
+        f64 = _fma_chain(rs, 1, 16, 1).astype(np.float64).view(np.uint64)
+        prods = {}
+        for name, kind, n, k, fp8 in (("bf16_16", 0, 16, 128, False), ("bf16_32", 2, 32, 128, False),
+                                      ("fp8", 4, 16, 256, True)):
+            oa = cu_sweep_operands(rs, kind, n, k, fp8)
+            ob = cu_sweep_operands(rs, kind + 1, n, k, fp8)
+            d = np.einsum("wik,wjk->wij", oa, ob)
+            peak = max(peak, int(np.einsum("wik,wjk->wij", np.abs(oa), np.abs(ob)).max()))
+            prods[name] = d.astype(np.float32).view(np.uint32)
+            out[name + "_a"].append(oa)
+            out[name + "_b"].append(ob)
+        row = np.concatenate([x, acc.view(np.uint32), f32, f64.view(np.uint32),
+                              prods["bf16_16"].ravel(), prods["bf16_32"].ravel(), prods["fp8"].ravel()])
+        assert row.size == CU_SWEEP_ROUND_WORDS
+        rows.append(row.astype(np.uint32))
+        for k, v in (("hash", x), ("mad", acc), ("f32", f32), ("f64", f64), ("bf16_16", prods["bf16_16"]),
+                     ("bf16_32", prods["bf16_32"]), ("fp8", prods["fp8"]),
+                     ("lds", cu_sweep_lds_words(seed, r, lds_bytes // 4))):
+            out[k].append(v)
+    res = {k: np.stack(v) for k, v in out.items()}
+    res["table"] = np.concatenate(rows)
+    res["peak"] = peak
+    return res

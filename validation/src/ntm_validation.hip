@@ -1,5 +1,6 @@
 // C ABI over the MI355X validation kernels (K1 GEMM, K2 HBM stream,
-// K3 fill/reference/verify, K4 HBM pattern test). Built for gfx950 only into
+// K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep).
+// Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
 // Every entry point is stream-ordered, allocation-free and sync-free, so it
@@ -11,6 +12,7 @@
 // The non-default K1 builds, schedule knobs and diagnostics live in
 // ntm_experimental.hip -> libntm_experimental.so (tests and tools only).
 #include "ntm/aux_kernels.hpp"
+#include "ntm/cu_sweep.hpp"
 #include "ntm/gemm_bf16_pp2.hpp"
 #include "ntm/gemm_bf16_pp3.hpp"
 #include "ntm/gemm_bf16_pp3h.hpp"
@@ -1252,4 +1254,72 @@ NTM_API int ntm_hbm_pattern_verify(void* ptr, size_t bytes, unsigned long long b
     else pattern_verify_p<kPatternHash, false>(ptr, n4, bw, seed, inv, result, S(stream));
   }
   return (int)hipGetLastError();
+}
+
+// K5: per-CU compute sweep (cu_sweep.hpp; record, decode, expected tables and
+// aggregation in cu_sweep_plan.hpp). ntm_cu_sweep_launch is one launch:
+// `records` (device, grid * 64 bytes) is zeroed and filled, `expected` (device)
+// holds ntm_cu_sweep_expected(iters, seed). fault_key = ~0u: no injection.
+// The decode / expected / summarize entry points are host-only: no GPU needed.
+NTM_API int ntm_cu_sweep_record_bytes() { return (int)sizeof(ntm::cus::Record); }
+
+NTM_API size_t ntm_cu_sweep_expected_bytes(int iters) {
+  return iters >= 1 && iters <= ntm::cus::kMaxIters ? ntm::cus::expected_bytes(iters) : 0;
+}
+
+NTM_API int ntm_cu_sweep_expected(int iters, unsigned seed, void* out, size_t out_bytes) {
+  if (!out || iters < 1 || iters > ntm::cus::kMaxIters || out_bytes < ntm::cus::expected_bytes(iters))
+    return (int)hipErrorInvalidValue;
+  ntm::cus::make_expected((uint32_t*)out, iters, seed);
+  return 0;
+}
+
+// The LDS fill pattern of round `round`: words first .. first + count.
+NTM_API int ntm_cu_sweep_lds_words(unsigned seed, unsigned round, unsigned first, unsigned count,
+                                   unsigned* out) {
+  if (!out) return (int)hipErrorInvalidValue;
+  const uint32_t rs = ntm::cus::round_seed(seed, round);
+  for (unsigned i = 0; i < count; ++i) out[i] = ntm::cus::lds_word(first + i, rs);
+  return 0;
+}
+
+// The device's per-block LDS maximum (the default lds_bytes), 0 on an error.
+NTM_API int ntm_cu_sweep_max_lds_bytes(int device) {
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return v / 16 * 16;
+}
+
+NTM_API int ntm_cu_sweep_launch(void* records, const void* expected, unsigned grid, int iters,
+                                size_t lds_bytes, unsigned seed, unsigned fault_key,
+                                int fault_subtest, void* stream) {
+  if ((uintptr_t)records % 8 || (uintptr_t)expected % 8) return (int)hipErrorInvalidValue;
+  return (int)ntm::cus::launch_cu_sweep((ntm::cus::Record*)records, (const uint32_t*)expected, grid,
+                                        iters, lds_bytes, seed, fault_key, fault_subtest, S(stream));
+}
+
+// out[0..5] = xcc, se, sh, cu, simd, packed key
+NTM_API void ntm_cu_sweep_decode(unsigned hw_id, unsigned xcc_id, unsigned* out) {
+  const ntm::cus::CuId id = ntm::cus::decode(hw_id, xcc_id);
+  out[0] = id.xcc, out[1] = id.se, out[2] = id.sh, out[3] = id.cu, out[4] = id.simd;
+  out[5] = ntm::cus::cu_key(hw_id, xcc_id);
+}
+
+// Aggregates n host records of `launches` launches on a device of `cus` CUs
+// into a JSON object (cu_sweep_plan.hpp summary_json). Returns the JSON's
+// length; it is written (NUL-terminated) only when it fits in `cap`.
+NTM_API size_t ntm_cu_sweep_summarize(const void* records, size_t n, unsigned cus, unsigned launches,
+                                      int gpu, char* json, size_t cap) {
+  ntm::cus::Sweep sweep;
+  std::vector<ntm::cus::Record> recs(n);
+  if (n) std::memcpy(recs.data(), records, n * sizeof(ntm::cus::Record));
+  sweep.add(recs.data(), n);
+  ntm::cus::Summary s = sweep.summary(cus);
+  s.launches = launches;
+  const std::string j = ntm::cus::summary_json(gpu, s);
+  if (json && j.size() < cap) std::memcpy(json, j.c_str(), j.size() + 1);
+  return j.size();
 }

@@ -9,6 +9,8 @@
 //   K2  HBM stream copy bandwidth + capacity check (288 GB class)
 //   K4  HBM pattern test over (up to) all free HBM, off by default
 //       (--hbm-test-gb; ntm/hbm_pattern.hpp)
+//   K5  per-CU compute sweep that names a bad CU, off by default
+//       (--cu-sweep; ntm/cu_sweep.hpp)
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL
@@ -40,6 +42,7 @@
 #include <unistd.h>
 
 #include "ntm/common.hpp"
+#include "ntm/cu_sweep_plan.hpp"
 #include "ntm/hbm_test_plan.hpp"
 
 namespace ntm {
@@ -83,6 +86,8 @@ int ntm_hbm_pattern_write(void*, size_t, unsigned long long, int, unsigned long 
 int ntm_hbm_pattern_verify(void*, size_t, unsigned long long, int, unsigned long long, int, int,
                            void*, void*);
 int ntm_hbm_pattern_result_bytes();
+int ntm_cu_sweep_launch(void*, const void*, unsigned, int, size_t, unsigned, unsigned, int, void*);
+int ntm_cu_sweep_max_lds_bytes(int);
 }
 
 namespace {
@@ -119,6 +124,8 @@ struct Opts {
   double hbm_floor_gbps = 0;
   double hbm_test_gb = 0;       // K4: 0 = off, < 0 = all free HBM minus the headroom
   int hbm_test_passes = 1;
+  bool cu_sweep = false;        // K5: off unless asked for
+  int cu_sweep_iters = 16;      // rounds per workgroup (profiles/cu_sweep/README.md)
   long allreduce_max_mib = 8192;  // 8 GiB, capped by free HBM
   bool xgmi = true;
   int xgmi_sim = 0;             // C2 with N simulated ranks on GPU 0 (one-GPU test path)
@@ -151,6 +158,7 @@ void usage() {
                "usage: amdgpu-validate [--gpus N] [--size 8192] [--iters 50]\n"
                "       [--tflops-floor TF] [--min-hbm-gb GB] [--hbm-floor-gbps GBps]\n"
                "       [--hbm-test-gb GB] [--hbm-test-passes P]\n"
+               "       [--cu-sweep] [--cu-sweep-iters N]\n"
                "       [--allreduce-max-mib MiB] [--rccl | --no-rccl] [--no-xgmi] [--xgmi-sim N]\n"
                "       [--settle-s S] [--no-fp8] [--fp8-tflops-floor TF]\n"
                "       [--no-p2p] [--p2p-mib MiB] [--p2p-floor-gbps GBps] [--p2p-loopback]\n"
@@ -162,12 +170,17 @@ void usage() {
                "       [--pushgateway http://host:port]\n"
                "fault-inject (also env NTM_FAULT_INJECT): corrupt_gemm | corrupt_abft |\n"
                "       corrupt_fp8 | corrupt_fp8_abft | corrupt_p2p | corrupt_allreduce |\n"
-               "       corrupt_hbm | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
+               "       corrupt_hbm | bad_cu | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
                "       launch claims a wrong XCD; corrupt_hbm: one bit of the pattern test's\n"
                "       last chunk, needs --hbm-test-gb) to prove detection\n"
                "hbm-test-gb: K4, write / read back / compare an address pattern and a hash\n"
                "       pattern over GB (1e9 bytes) of each GPU's HBM; 0 = off (default), -1 = all\n"
-               "       free HBM minus max(2 GiB, 2 %%); hbm-test-passes: repeat it P times\n");
+               "       free HBM minus max(2 GiB, 2 %%); hbm-test-passes: repeat it P times\n"
+               "cu-sweep: K5, known-answer LDS / VALU / MFMA sub-tests on every CU (4 workgroups\n"
+               "       per CU and launch, up to 8 launches until every CU ran one); a failure\n"
+               "       names xcd, se, sh, cu and simd; cu-sweep-iters: rounds per workgroup\n"
+               "       (default 16). fault-inject bad_cu (needs --cu-sweep): the workgroups on one\n"
+               "       CU of the LAST GPU flip one bit of a computed value\n");
 }
 
 bool parse(int argc, char** argv, Opts& o) {
@@ -188,6 +201,8 @@ bool parse(int argc, char** argv, Opts& o) {
     else if (a == "--min-hbm-gb") { if (!(v = next(a.c_str()))) return false; o.min_hbm_gb = std::atof(v); }
     else if (a == "--hbm-floor-gbps") { if (!(v = next(a.c_str()))) return false; o.hbm_floor_gbps = std::atof(v); }
     else if (a == "--hbm-test-gb") { if (!(v = next(a.c_str()))) return false; o.hbm_test_gb = std::atof(v); }
+    else if (a == "--cu-sweep") o.cu_sweep = true;
+    else if (a == "--cu-sweep-iters") { if (!(v = next(a.c_str()))) return false; o.cu_sweep_iters = std::atoi(v); }
     else if (a == "--hbm-test-passes") { if (!(v = next(a.c_str()))) return false; o.hbm_test_passes = std::atoi(v); }
     else if (a == "--allreduce-max-mib") { if (!(v = next(a.c_str()))) return false; o.allreduce_max_mib = std::atol(v); }
     else if (a == "--no-xgmi") o.xgmi = false;
@@ -220,7 +235,8 @@ bool parse(int argc, char** argv, Opts& o) {
   }
   return o.size > 0 && o.iters > 0 && o.p2p_mib > 0 && o.allreduce_max_mib > 0 &&
          o.xgmi_sim >= 0 && o.xgmi_sim <= ntm::xgmi::kMaxRanks && o.settle_s >= 0 &&
-         o.hbm_test_passes >= 1 && std::isfinite(o.hbm_test_gb);
+         o.hbm_test_passes >= 1 && std::isfinite(o.hbm_test_gb) && o.cu_sweep_iters >= 1 &&
+         o.cu_sweep_iters <= ntm::cus::kMaxIters;
 }
 
 // ------------------------------------------------------------ JSON helpers
@@ -320,6 +336,12 @@ struct GpuResult {
   double hbm_test_alloc_s = 0, hbm_test_free_s = 0;
   std::string hbm_test_steps;    // JSON array of per-step seconds
   std::string hbm_test_failure;  // empty = clean
+  // K5 (only with --cu-sweep)
+  bool cu_sweep_ran = false;
+  ntm::cus::Summary cu_sweep;
+  int cu_sweep_lds_bytes = 0;
+  double cu_sweep_s = 0;
+  std::string cu_sweep_failure;  // empty = clean
 };
 
 // The split-mode self-check shape: 48 x 5 of 192x256 tiles, half a round on
@@ -469,6 +491,65 @@ bool run_hbm_test(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r
   for (auto& c : chunks) CK(hipFree(c.p));
   r.hbm_test_free_s = since(t_free);
   r.hbm_test_s = since(t_begin);
+  return true;
+}
+
+// ---- K5: per-CU compute sweep (ntm/cu_sweep.hpp, host side in ntm/cu_sweep_plan.hpp).
+// Launches of 4 workgroups per CU until every CU ran one, at most kMaxLaunches: a CU
+// that never ran fails the check. bad_cu: a clean launch learns the CU keys, then the
+// sweep runs with the middle key of the sorted list as the CU that flips a bit.
+bool run_cu_sweep(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r) {
+  namespace cu = ntm::cus;
+  const auto t_begin = Clock::now();
+  hipDeviceProp_t prop;
+  CK(hipGetDeviceProperties(&prop, dev));
+  const uint32_t cus = (uint32_t)prop.multiProcessorCount;
+  const unsigned grid = cu::kGridPerCu * cus;
+  const int lds = ntm_cu_sweep_max_lds_bytes(dev);
+  r.cu_sweep_ran = true;
+  r.cu_sweep_lds_bytes = lds;
+  if (lds < 16 || cus == 0) {
+    r.cu_sweep_failure = "gpu" + std::to_string(dev) + ": CU sweep: cannot read the device's LDS size or CU count";
+    return true;
+  }
+  const int iters = o.cu_sweep_iters;
+  std::vector<uint32_t> table(cu::expected_bytes(iters) / 4);
+  void *dexp = nullptr, *drec = nullptr;
+  CK(hipMalloc(&dexp, table.size() * 4));
+  CK(hipMalloc(&drec, (size_t)grid * sizeof(cu::Record)));
+  uint32_t fault_key = cu::kFaultOff;
+  bool hip_ok = true;
+  auto launch = [&](int l, std::vector<cu::Record>& recs) -> bool {
+    // a new seed per launch: new tables, so repeated launches do not repeat the data
+    cu::make_expected(table.data(), iters, (uint32_t)l);
+    recs.resize(grid);
+    hip_ok = hipMemcpyAsync(dexp, table.data(), table.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess &&
+             ntm_cu_sweep_launch(drec, dexp, grid, iters, (size_t)lds, (unsigned)l, fault_key,
+                                 cu::kSubBf16, s) == 0 &&
+             hipMemcpyAsync(recs.data(), drec, recs.size() * sizeof(cu::Record), hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipStreamSynchronize(s) == hipSuccess;
+    return hip_ok;
+  };
+  if (last && o.fault == "bad_cu") {
+    cu::Sweep probe;
+    std::vector<cu::Record> recs;
+    if (launch(0, recs)) {
+      probe.add(recs.data(), recs.size());
+      const std::vector<uint32_t> keys = probe.keys();  // sorted
+      if (!keys.empty()) fault_key = keys[keys.size() / 2];
+    }
+  }
+  cu::Sweep sweep;
+  if (hip_ok) cu::coverage_loop(cus, cu::kMaxLaunches, launch, sweep);
+  if (!hip_ok) {
+    fail("gpu" + std::to_string(dev) + ": CU sweep: HIP error " + hipGetErrorString(hipGetLastError()));
+    return false;
+  }
+  r.cu_sweep = sweep.summary(cus);
+  r.cu_sweep_failure = cu::failure_message(dev, r.cu_sweep);
+  CK(hipFree(dexp));
+  CK(hipFree(drec));
+  r.cu_sweep_s = std::chrono::duration<double>(Clock::now() - t_begin).count();
   return true;
 }
 
@@ -708,6 +789,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   CK(hipFree(src));
   CK(hipFree(dst));
   if (o.hbm_test_gb != 0 && !run_hbm_test(dev, last, o, s, r)) return false;
+  if (o.cu_sweep && !run_cu_sweep(dev, last, o, s, r)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));
@@ -1400,6 +1482,7 @@ int main(int argc, char** argv) {
       fail(d + "HBM " + jnum(r.total_gb) + " GB below " + jnum(o.min_hbm_gb) + " GB");
     if (!r.hbm_copy_ok) fail(d + "HBM copy mismatch");
     if (!r.hbm_test_failure.empty()) fail(r.hbm_test_failure);
+    if (!r.cu_sweep_failure.empty()) fail(r.cu_sweep_failure);
     if (o.hbm_floor_gbps > 0 && r.hbm_copy_gbps < o.hbm_floor_gbps)
       fail(d + "HBM copy " + jnum(r.hbm_copy_gbps) + " GB/s below floor");
   }
@@ -1470,6 +1553,18 @@ int main(int argc, char** argv) {
         if (r.hbm_test_ran)
           p << "amdgpu_validate_hbm_test_bad_words{gpu=\"" << r.device << "\"} " << r.hbm_test_bad_words << "\n";
     }
+    if (o.cu_sweep) {
+      p << "# HELP amdgpu_validate_cu_sweep_cus_covered Compute units that ran a workgroup of the CU sweep.\n"
+        << "# TYPE amdgpu_validate_cu_sweep_cus_covered gauge\n";
+      for (auto& r : res)
+        if (r.cu_sweep_ran)
+          p << "amdgpu_validate_cu_sweep_cus_covered{gpu=\"" << r.device << "\"} " << r.cu_sweep.cus_covered << "\n";
+      p << "# HELP amdgpu_validate_cu_sweep_bad_cus Compute units with a wrong known-answer result.\n"
+        << "# TYPE amdgpu_validate_cu_sweep_bad_cus gauge\n";
+      for (auto& r : res)
+        if (r.cu_sweep_ran)
+          p << "amdgpu_validate_cu_sweep_bad_cus{gpu=\"" << r.device << "\"} " << r.cu_sweep.bad_cus.size() << "\n";
+    }
     if (!rccl_rows.empty() || !xgmi_rows.empty())
       p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
         << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(peak_rccl) << "\n"
@@ -1530,6 +1625,14 @@ int main(int argc, char** argv) {
             ",\"hbm_test_alloc_s\":" + jnum(r.hbm_test_alloc_s) +
             ",\"hbm_test_free_s\":" + jnum(r.hbm_test_free_s) +
             ",\"hbm_test_steps\":" + (r.hbm_test_steps.empty() ? std::string("[]") : r.hbm_test_steps);
+    if (r.cu_sweep_ran)
+      js += ",\"cu_sweep_cus\":" + std::to_string(r.cu_sweep.cus) +
+            ",\"cu_sweep_cus_covered\":" + std::to_string(r.cu_sweep.cus_covered) +
+            ",\"cu_sweep_simds_covered\":" + std::to_string(r.cu_sweep.simds_covered) +
+            ",\"cu_sweep_launches\":" + std::to_string(r.cu_sweep.launches) +
+            ",\"cu_sweep_bad_cus\":" + ntm::cus::bad_cus_json(r.cu_sweep) +
+            ",\"cu_sweep_lds_bytes\":" + std::to_string(r.cu_sweep_lds_bytes) +
+            ",\"cu_sweep_s\":" + jnum(r.cu_sweep_s);
     js += "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(rccl_rows);
