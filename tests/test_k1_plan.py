@@ -1,4 +1,4 @@
-"""Host-side K1 dispatch plan (``ntm_k1_plan``, validation/src/ntm_validation.hip):
+"""Host-side K1 dispatch plan (``ntm_k1_plan``, validation/include/ntm/k1_plan.hpp):
 which rows of C go on the 256x256 kernel and which small tile takes the rest.
 No GPU needed - the plan is pure host code in the native library."""
 import pytest
@@ -284,7 +284,7 @@ def test_plan_tie_prefers_fewer_tiles(k1_plan, m, n, k):
     (4096, 4100, 4096, False),   # N % 8 != 0
 ])
 def test_stream_k_decomposition_serves(k1_plan, m, n, k, served):
-    """sk_decompose (gemm_bf16_sk.hpp), seen through the host-side workspace
+    """sk_decompose (k1_plan.hpp), seen through the host-side workspace
     query: which shapes stream-K's two-round and split modes serve."""
     from nvidia_terraform_modules_amd import ops
 

@@ -76,6 +76,21 @@ struct GemmArgs {
   unsigned long long* stamps = nullptr;
 };
 
+inline GemmArgs make_args(const void* A, const void* B, void* C, int M, int N, int K, int lda,
+                          int ldb, int ldc) {
+  GemmArgs a;
+  a.A = (const __bf16*)A;
+  a.B = (const __bf16*)B;
+  a.C = (__bf16*)C;
+  a.M = M;
+  a.N = N;
+  a.K = K;
+  a.lda = lda;
+  a.ldb = ldb;
+  a.ldc = ldc;
+  return a;
+}
+
 // Shapes the fast kernel accepts; the host launcher rejects anything else.
 __host__ __device__ inline bool shape_ok(int M, int N, int K) {
   return M > 0 && N > 0 && K >= 2 * BK && (M % BM) == 0 && (N % BN) == 0 &&

@@ -1,6 +1,6 @@
 // K1 "pingpong8o" (variant 25): persistent pingpong8c whose C stores OVERLAP
 // the next tile's K loop. The default plan runs it in place of pingpong8c when
-// the 256x256 part has more tiles than CUs (ntm_validation.hip plan_k1).
+// the 256x256 part has more tiles than CUs (k1_plan.hpp plan_search).
 //
 // Why: at 8192^3 every CU runs 4 tiles back to back, and each tile boundary
 // costs ~5 us of wall in the data-parallel kernel (profiles/r2_k1/
@@ -49,6 +49,7 @@
 #pragma once
 
 #include "ntm/gemm_bf16_pp3.hpp"
+#include "ntm/k1_plan.hpp"
 
 namespace ntm {
 namespace gemm6 {
@@ -58,9 +59,7 @@ using ::ntm::gemm3::Frags3;
 using ::ntm::gemm3::kLdsBytes3;
 using ::ntm::gemm3::kScratch;
 
-__host__ __device__ inline bool shape_ok6(int M, int N, int K) {
-  return M > 0 && N > 0 && (M % BM) == 0 && (N % BN) == 0 && (K % (2 * BK)) == 0 && K >= 4 * BK;
-}
+using ::ntm::k1::shape_ok6;  // the plan prices K1-fp8's persistent rule with it
 
 // Masked build ("pingpong8om"): ragged C (any M, N % 8) on whole K-tile pairs
 // (K % 128, K >= 256); edge tiles clamp their source rows and mask their stores.

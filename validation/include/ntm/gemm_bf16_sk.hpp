@@ -62,6 +62,7 @@
 #pragma once
 
 #include "ntm/gemm_bf16_pp3.hpp"
+#include "ntm/k1_plan.hpp"
 
 namespace ntm {
 namespace gemmsk {
@@ -73,11 +74,14 @@ using ::ntm::gemm3::kEpiDefault;
 using ::ntm::gemm3::kLdsBytes3;
 using ::ntm::gemm3::tile3;
 
-constexpr size_t kPartialBytes = (size_t)BM * BN * 4;  // one fp32 256x256 partial
-constexpr size_t kCounterBytes = 4096;                 // counter block at the workspace start
-// error word (last of the counter block): 0, or the first XCD-placement
-// violation a combiner saw: 0x80000000 | mode << 28 | tile << 8 | mine << 4 | other
-constexpr int kErrWord = (int)(kCounterBytes / 4) - 1;
+// the workspace layout and the host shape rules are the plan's (k1_plan.hpp)
+static_assert(BM == ::ntm::k1::kBM && BN == ::ntm::k1::kBN && BK == ::ntm::k1::kBK, "256x256x64");
+using ::ntm::k1::kCounterBytes;
+using ::ntm::k1::kErrWord;
+using ::ntm::k1::kMaxSlices;
+using ::ntm::k1::kPartialBytes;
+using ::ntm::k1::shape_ok_sk;
+using ::ntm::k1::sk_ws_bytes;
 // two-round mode: the head's / tail's XCC tag (id + 1) above the protocol bits
 constexpr int kHeadTagShift = 8, kTailTagShift = 16;
 
@@ -102,41 +106,17 @@ inline unsigned& sk_fault_inject() {
   return v;
 }
 
-// Tiles, pairs and the whole-tile prefix for (M, N, K) on `cus` CUs.
-// Two-round mode (S = 0): more tiles than CUs, not a multiple of them.
-// Split mode (S >= 2, gemm_bf16_sks_kernel): every XCD's tiles fit its CUs at
-// least twice over, so each tile is cut into S equal K slices and every slice
-// runs at once on its own CU (one round, slices at the same K offsets in
-// lockstep); S = the most slices that fit, at most kMaxSlices and one pair each.
-constexpr int kMaxSlices = 8;
-
-__host__ __device__ inline bool sk_decompose(int M, int N, int K, int cus, SkArgs& s) {
-  // one 4-byte counter per workgroup slot (or per tile) in the kCounterBytes block
-  if (M <= 0 || N <= 0 || K <= 0 || cus < 8 || (cus % 8) != 0 || cus + 8 > kErrWord)
-    return false;
-  s.ntiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  s.G = cus;
-  s.Tp = (K + 2 * BK - 1) / (2 * BK);
-  s.S = 0;
-  if (s.ntiles <= s.G) {
-    const int per_xcd = (s.ntiles + 7) / 8, W = s.G / 8;
-    int S = W / per_xcd;
-    if (S > kMaxSlices) S = kMaxSlices;
-    if (S > s.Tp) S = s.Tp;
-    if (S < 2) return false;
-    s.S = S;
-    s.D = 0;
-    return true;
-  }
-  if ((s.ntiles % s.G) == 0) return false;
-  s.D = (s.ntiles / s.G - 1) * s.G;
-  return true;
+// The decomposition of (M, N, K) in TM x TN tiles on `cus` CUs (k1_plan.hpp
+// sk_decompose: two-round and split mode) into the kernel's arguments.
+template <int TM, int TN, bool kTwoRound>
+NTM_HD inline bool sk_decompose_into(int M, int N, int K, int cus, SkArgs& s) {
+  ::ntm::k1::SkShape d;
+  const bool ok = ::ntm::k1::sk_decompose<TM, TN, kTwoRound>(M, N, K, cus, d);
+  s.G = d.G, s.D = d.D, s.Tp = d.Tp, s.ntiles = d.ntiles, s.S = d.S;
+  return ok;
 }
-
-inline size_t sk_ws_bytes(int G) { return kCounterBytes + (size_t)G * 2 * kPartialBytes; }
-
-__host__ __device__ inline bool shape_ok_sk(int M, int N, int K) {
-  return M > 0 && N > 0 && (N % 8) == 0 && K >= 2 * BK && (K % 8) == 0;
+NTM_HD inline bool sk_decompose(int M, int N, int K, int cus, SkArgs& s) {
+  return sk_decompose_into<BM, BN, true>(M, N, K, cus, s);
 }
 
 // Clamped per-lane sources of tile (m0, n0) at K-tile 0 (pingpong8cm's setup).

@@ -32,21 +32,8 @@ using ::ntm::gemm3h::Geo;
 
 // Split mode only: every XCD's TM x TN tiles fit its CUs at least twice.
 template <int TM, int TN>
-__host__ __device__ inline bool sk_decompose_h(int M, int N, int K, int cus, SkArgs& s) {
-  if (M <= 0 || N <= 0 || K <= 0 || cus < 8 || (cus % 8) != 0 || cus + 8 > kErrWord) return false;
-  s.ntiles = ((M + TM - 1) / TM) * ((N + TN - 1) / TN);
-  s.G = cus;
-  s.Tp = (K + 2 * BK - 1) / (2 * BK);
-  s.D = 0;
-  s.S = 0;
-  if (s.ntiles > s.G) return false;
-  const int per_xcd = (s.ntiles + 7) / 8, W = s.G / 8;
-  int S = W / per_xcd;
-  if (S > kMaxSlices) S = kMaxSlices;
-  if (S > s.Tp) S = s.Tp;
-  if (S < 2) return false;
-  s.S = S;
-  return true;
+NTM_HD inline bool sk_decompose_h(int M, int N, int K, int cus, SkArgs& s) {
+  return sk_decompose_into<TM, TN, false>(M, N, K, cus, s);
 }
 
 // The accumulators the tile uses: the A-hi (mh = 1) half has kMtHi m-tiles per

@@ -40,6 +40,7 @@
 #pragma once
 
 #include "ntm/gemm_bf16.hpp"
+#include "ntm/k1_plan.hpp"
 
 namespace ntm {
 namespace gemmt {
@@ -635,8 +636,9 @@ inline hipError_t launch_gemm_fp8_tile_ws(const void* A, const void* B, __bf16* 
 // kernel on a (tiles, S) grid writes fp32 partials to ws (S M N floats), then
 // splitk_reduce_kernel sums them into C. For C too small to fill the chip
 // with a long K (hipBLASLt's GSU kernels serve these shapes the same way).
-inline int splitk_kc(int K, int S) { return ((K + S - 1) / S + TK - 1) / TK * TK; }
-inline int splitk_slices(int K, int S) { const int kc = splitk_kc(K, S); return (K + kc - 1) / kc; }
+static_assert(TK == ::ntm::k1::kSplitKTile, "the plan slices K by this kernel's K tile");
+using ::ntm::k1::splitk_kc;
+using ::ntm::k1::splitk_slices;
 
 template <int MT, int NT>
 inline hipError_t launch_gemm_bf16_tile_ws_splitk(const GemmArgs& a, int S, float* ws,

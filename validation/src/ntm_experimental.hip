@@ -39,28 +39,14 @@
 
 namespace {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-ntm::gemm::GemmArgs args(const void* A, const void* B, void* C, int M, int N, int K, int lda,
-                         int ldb, int ldc) {
-  ntm::gemm::GemmArgs a;
-  a.A = (const __bf16*)A;
-  a.B = (const __bf16*)B;
-  a.C = (__bf16*)C;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
-  return a;
-}
+using ntm::gemm::make_args;
 }  // namespace
 
 NTM_API const char* ntm_experimental_version() { return "ntm-experimental 0.2.0 gfx950"; }
 
 NTM_API int ntm_gemm_bf16_experimental(int variant, const void* A, const void* B, void* C, int M,
                                        int N, int K, int lda, int ldb, int ldc, void* stream) {
-  const ntm::gemm::GemmArgs a = args(A, B, C, M, N, K, lda, ldb, ldc);
+  const ntm::gemm::GemmArgs a = make_args(A, B, C, M, N, K, lda, ldb, ldc);
   switch (variant) {
     case 1: return (int)ntm::gemm::launch_gemm_bf16(a, S(stream));
     case 10:
@@ -116,16 +102,7 @@ NTM_API int ntm_gemm_bf16_experimental(int variant, const void* A, const void* B
 NTM_API int ntm_gemm_bf16_sk_rev(const void* A, const void* B, void* C, int M, int N, int K,
                                  int lda, int ldb, int ldc, void* ws, size_t ws_bytes,
                                  void* stream) {
-  ntm::gemm::GemmArgs a;
-  a.A = (const __bf16*)A;
-  a.B = (const __bf16*)B;
-  a.C = (__bf16*)C;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
+  const ntm::gemm::GemmArgs a = make_args(A, B, C, M, N, K, lda, ldb, ldc);
   return (int)ntm::gemmsk::launch_gemm_bf16_sk<true>(a, ntm::gemm6::pp6_grid(1 << 30), ws,
                                                      ws_bytes, S(stream));
 }
@@ -134,16 +111,7 @@ NTM_API int ntm_gemm_bf16_sk_rev(const void* A, const void* B, void* C, int M, i
 NTM_API int ntm_gemm_bf16_sk_stamp(const void* A, const void* B, void* C, int M, int N, int K,
                                    int lda, int ldb, int ldc, void* ws, size_t ws_bytes,
                                    void* stamps, void* stream) {
-  ntm::gemm::GemmArgs a;
-  a.A = (const __bf16*)A;
-  a.B = (const __bf16*)B;
-  a.C = (__bf16*)C;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
+  const ntm::gemm::GemmArgs a = make_args(A, B, C, M, N, K, lda, ldb, ldc);
   return (int)ntm::gemmsk::launch_gemm_bf16_sk<false, true>(
       a, ntm::gemm6::pp6_grid(1 << 30), ws, ws_bytes, S(stream), (unsigned long long*)stamps);
 }
@@ -153,7 +121,7 @@ NTM_API int ntm_gemm_bf16_sk_stamp(const void* A, const void* B, void* C, int M,
 NTM_API int ntm_gemm_bf16_sk_nopair(const void* A, const void* B, void* C, int M, int N, int K,
                                     int lda, int ldb, int ldc, void* ws, size_t ws_bytes,
                                     void* stream) {
-  const ntm::gemm::GemmArgs a = args(A, B, C, M, N, K, lda, ldb, ldc);
+  const ntm::gemm::GemmArgs a = make_args(A, B, C, M, N, K, lda, ldb, ldc);
   return (int)ntm::gemmsk::launch_gemm_bf16_sk<false, false, false>(
       a, ntm::gemm6::pp6_grid(1 << 30), ws, ws_bytes, S(stream));
 }
@@ -162,7 +130,7 @@ NTM_API int ntm_gemm_bf16_sk_nopair(const void* A, const void* B, void* C, int M
 // workgroup's last tile cut by 2 * cut_pairs K-tiles (C is WRONG; timing only).
 NTM_API int ntm_gemm_bf16_pp6_oddcut(int cut_pairs, const void* A, const void* B, void* C, int M,
                                      int N, int K, int lda, int ldb, int ldc, void* stream) {
-  ntm::gemm::GemmArgs a = args(A, B, C, M, N, K, lda, ldb, ldc);
+  ntm::gemm::GemmArgs a = make_args(A, B, C, M, N, K, lda, ldb, ldc);
   a.splitk_kc = cut_pairs;
   return (int)ntm::gemm6::launch_gemm_bf16_pp6<1, 3, true>(a, S(stream));
 }
@@ -174,7 +142,7 @@ NTM_API int ntm_gemm_bf16_pp6_oddcut(int cut_pairs, const void* A, const void* B
 NTM_API int ntm_gemm_bf16_pp6_stamp(int grid, int store, const void* A, const void* B, void* C,
                                     int M, int N, int K, int lda, int ldb, int ldc, void* stamps,
                                     void* stream) {
-  ntm::gemm::GemmArgs a = args(A, B, C, M, N, K, lda, ldb, ldc);
+  ntm::gemm::GemmArgs a = make_args(A, B, C, M, N, K, lda, ldb, ldc);
   a.stamps = (unsigned long long*)stamps;
   if (grid * 2 > (M / 256) * (N / 256)) return (int)hipErrorInvalidValue;
   using namespace ntm::gemm6;
@@ -189,8 +157,8 @@ NTM_API int ntm_gemm_bf16_pp6_stamp(int grid, int store, const void* A, const vo
 // pingpong8c tuning knobs (see launch_gemm_bf16_pp3_knob).
 NTM_API int ntm_gemm_bf16_knob(int knob, const void* A, const void* B, void* C, int M, int N,
                                int K, int lda, int ldb, int ldc, void* stream) {
-  return (int)ntm::gemm3::launch_gemm_bf16_pp3_knob(args(A, B, C, M, N, K, lda, ldb, ldc), knob,
-                                                    S(stream));
+  return (int)ntm::gemm3::launch_gemm_bf16_pp3_knob(make_args(A, B, C, M, N, K, lda, ldb, ldc),
+                                                    knob, S(stream));
 }
 
 // pingpong8c ablation builds with s_memtime stamps (gemm_bf16_pp3_stamp.hpp;
@@ -198,8 +166,8 @@ NTM_API int ntm_gemm_bf16_knob(int knob, const void* A, const void* B, void* C, 
 // stamps: (M/256)*(N/256)*8*4 u64.
 NTM_API int ntm_gemm_bf16_stamp(int mode, const void* A, const void* B, void* C, int M, int N,
                                 int K, int lda, int ldb, int ldc, void* stamps, void* stream) {
-  return (int)ntm::gemm3s::launch_gemm_bf16_pp3_stamp(args(A, B, C, M, N, K, lda, ldb, ldc), mode,
-                                                      (unsigned long long*)stamps, S(stream));
+  return (int)ntm::gemm3s::launch_gemm_bf16_pp3_stamp(make_args(A, B, C, M, N, K, lda, ldb, ldc),
+                                                      mode, (unsigned long long*)stamps, S(stream));
 }
 
 // Matrix-core issue rate (gemm_fp8_diag.hpp mfma_rate_kernel): f8 0 = bf16
@@ -262,7 +230,7 @@ static hipError_t ws_knob(const ntm::gemm::GemmArgs& a, int knob, hipStream_t s)
 
 NTM_API int ntm_gemm_bf16_ws_knob(int shape, int knob, const void* A, const void* B, void* C,
                                   int M, int N, int K, int lda, int ldb, int ldc, void* stream) {
-  const ntm::gemm::GemmArgs a = args(A, B, C, M, N, K, lda, ldb, ldc);
+  const ntm::gemm::GemmArgs a = make_args(A, B, C, M, N, K, lda, ldb, ldc);
   switch (shape) {
     case 0: return (int)ws_knob<4, 4>(a, knob, S(stream));
     case 1: return (int)ws_knob<8, 4>(a, knob, S(stream));
