@@ -51,6 +51,13 @@ locals {
     var.validation_require_iommu_pt ? ["--require-iommu-pt"] : [],
     # K5: the per-CU compute sweep, off unless asked for
     var.validation_cu_sweep ? ["--cu-sweep"] : [],
+    # K6: the host-link (PCIe) check, off unless asked for; the floor only with it
+    var.validation_host_link_mib != 0 ? [
+      "--host-link-mib", tostring(var.validation_host_link_mib),
+    ] : [],
+    var.validation_host_link_mib != 0 && var.validation_host_link_floor_gbps != 0 ? [
+      "--host-link-floor-gbps", tostring(var.validation_host_link_floor_gbps),
+    ] : [],
     # one-line verdict surfaced as the pod's termination message
     ["--termination-log", "/dev/termination-log"],
   )

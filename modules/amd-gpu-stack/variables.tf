@@ -318,6 +318,28 @@ variable "validation_cu_sweep" {
   description = "Run the Job's per-CU compute sweep (K5): known-answer LDS, VALU, bf16 MFMA and fp8 MFMA sub-tests on every compute unit, 4 workgroups per CU and launch until every CU ran one (at most 8 launches). A wrong result fails the Job and names the XCD, SE, SH, CU and SIMD; a CU that ran no workgroup fails it too. Measurements: profiles/cu_sweep/README.md."
 }
 
+variable "validation_host_link_mib" {
+  type        = number
+  default     = 0
+  description = "Run the Job's host-link (PCIe) check (K6) on this many MiB of pinned host memory per GPU (0 = off): the GPU writes a hash pattern into host memory, reads it back over the link and compares on the device, runs both directions at once, times hipMemcpyAsync both ways on the same buffers and measures the read round-trip latency. A word that crosses the link wrong fails the Job; the message names the GPU, the direction, the byte offset, expected, got and the bad bits. Measurements: profiles/host_link/README.md."
+
+  validation {
+    condition     = var.validation_host_link_mib >= 0
+    error_message = "validation_host_link_mib must be >= 0 (0 = off)."
+  }
+}
+
+variable "validation_host_link_floor_gbps" {
+  type        = number
+  default     = 0
+  description = "Per-direction host-link rate in GB/s below which the Job fails, applied to the faster of the check's kernel and hipMemcpyAsync (0 = report only; needs validation_host_link_mib). Catches a link trained down to x8 or Gen3 and a translating IOMMU. Set it from a node's first measurement: profiles/host_link/README.md."
+
+  validation {
+    condition     = var.validation_host_link_floor_gbps >= 0
+    error_message = "validation_host_link_floor_gbps must be >= 0 (0 = report only)."
+  }
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

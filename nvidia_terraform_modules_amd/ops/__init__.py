@@ -12,6 +12,8 @@ K4 ``hbm_pattern_write``, ``hbm_pattern_verify`` - address / hash pattern fill a
    on-device compare for the full-capacity HBM test.
 K5 ``cu_sweep``, ``cu_sweep_decode``, ``cu_sweep_summarize`` - known-answer LDS / VALU /
    MFMA sub-tests per workgroup, tied to the CU that ran them.
+K6 ``host_link_push``, ``host_link_pull``, ``host_link_chase`` - the same pattern written to and
+   read from pinned host memory over the host link (PCIe), and its read round-trip latency.
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -61,6 +63,11 @@ from .kernels import (  # noqa: F401
     HbmPatternReport,
     hbm_pattern_verify,
     hbm_pattern_write,
+    host_link_chase,
+    host_link_default_blocks,
+    host_link_pull,
+    host_link_push,
+    host_link_tile_bytes,
     CU_SWEEP_SUBTESTS,
     cu_sweep,
     cu_sweep_decode,

@@ -100,6 +100,19 @@ def _declare(lib: ctypes.CDLL) -> None:
         "ntm_hbm_pattern_verify": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
                                     c_int, c_vp, c_vp], c_int),
         "ntm_hbm_pattern_result_bytes": ([], c_int),
+        "ntm_host_link_default_blocks": ([c_int], c_int),
+        "ntm_host_link_tile_bytes": ([c_int], c_int),
+        "ntm_host_link_push": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
+                                c_int, c_vp], c_int),
+        "ntm_host_link_push_ex": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
+                                   c_int, c_int, c_int, c_vp], c_int),
+        "ntm_host_link_pull": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
+                                c_vp, c_int, c_vp, c_vp], c_int),
+        "ntm_host_link_pull_ex": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
+                                   c_vp, c_int, c_int, c_int, c_vp, c_vp], c_int),
+        "ntm_host_link_chase": ([c_vp, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_vp,
+                                 c_vp], c_int),
+        "ntm_host_link_clock_khz": ([c_int], c_int),
         "ntm_cu_sweep_record_bytes": ([], c_int),
         "ntm_cu_sweep_expected_bytes": ([c_int], c_size),
         "ntm_cu_sweep_expected": ([c_int, ctypes.c_uint, c_vp, c_size], c_int),

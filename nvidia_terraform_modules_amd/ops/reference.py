@@ -131,6 +131,65 @@ def hbm_pattern_verify(t: torch.Tensor, pattern, seed: int = 0, invert: bool = F
         first_bad_offset=base + 8 * int(idx[0]) if idx.size else None, records=recs)
 
 
+# K6 on the CPU: the host-link kernels write and check K4's pattern, so push / pull are
+# hbm_pattern_write / hbm_pattern_verify on a plain CPU tensor (nothing crosses a link;
+# blocks only shapes the launch), and the chase is a numpy walk.
+HOST_LINK_SLOT_BYTES = 64
+
+
+def host_link_push(host: torch.Tensor, pattern, seed: int = 0, invert: bool = False,
+                   base: int = 0, blocks=None) -> torch.Tensor:
+    return hbm_pattern_write(host, pattern, seed=seed, invert=invert, base=base)
+
+
+def host_link_pull(host: torch.Tensor, pattern, seed: int = 0, invert: bool = False,
+                   base: int = 0, dst: torch.Tensor | None = None, blocks=None) -> HbmPatternReport:
+    rep = hbm_pattern_verify(host, pattern, seed=seed, invert=invert, base=base)
+    if dst is not None:
+        _bytes_of(dst)[:] = _bytes_of(host)
+    return rep
+
+
+def _splitmix64(state: int) -> tuple[int, int]:
+    m = 2**64 - 1
+    state = (state + 0x9E3779B97F4A7C15) & m
+    z = state
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return state, z ^ (z >> 31)
+
+
+def host_link_chase_next(nslots: int, seed: int = 0) -> np.ndarray:
+    """next[i] of the chase: Sattolo's algorithm on splitmix64(seed), one cycle of length
+    ``nslots`` (the same permutation as host_link_plan.hpp chase_permutation)."""
+    nxt = list(range(nslots))
+    s = seed & (2**64 - 1)
+    for i in range(nslots - 1, 0, -1):
+        s, z = _splitmix64(s)
+        j = z % i
+        nxt[i], nxt[j] = nxt[j], nxt[i]
+    return np.asarray(nxt, dtype=np.uint64)
+
+
+def host_link_chase_table(nslots: int, seed: int = 0) -> np.ndarray:
+    """The chase laid out as the kernel reads it: uint64 [nslots, 8], one 64-byte slot per
+    hop, word 0 = the next slot's index."""
+    table = np.zeros((nslots, HOST_LINK_SLOT_BYTES // 8), dtype=np.uint64)
+    table[:, 0] = host_link_chase_next(nslots, seed)
+    return table
+
+
+def host_link_chase(host: torch.Tensor, hops: int, start: int = 0) -> tuple[int, float]:
+    """The walk on the host: (final slot index, 0.0 - no link, no latency)."""
+    nxt = _bytes_of(host).view(np.uint64).reshape(-1, HOST_LINK_SLOT_BYTES // 8)[:, 0]
+    if not 0 <= start < len(nxt) or hops < 1:
+        raise ValueError("host_link_chase needs 0 <= start < slots and hops >= 1")
+    i = start
+    for _ in range(hops):
+        i = int(nxt[i])
+    return i, 0.0
+
+
 # K5 on the CPU: the expected tables of the per-CU compute sweep, written from the
 # definitions in validation/include/ntm/cu_sweep_plan.hpp with numpy integer arithmetic
 # (uint32 / uint64 wrap-around, int64 sums). One round = 7680 32-bit words:

@@ -1,5 +1,6 @@
 // C ABI over the MI355X validation kernels (K1 GEMM, K2 HBM stream,
-// K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep).
+// K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep,
+// K6 host-link check).
 // Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
@@ -23,6 +24,7 @@
 #include "ntm/gemm_fp8.hpp"
 #include "ntm/gemm_w4k.hpp"
 #include "ntm/hbm_pattern.hpp"
+#include "ntm/host_link.hpp"
 
 #define NTM_API extern "C" __attribute__((visibility("default")))
 
@@ -837,4 +839,154 @@ NTM_API size_t ntm_cu_sweep_summarize(const void* records, size_t n, unsigned cu
   const std::string j = ntm::cus::summary_json(gpu, s);
   if (json && j.size() < cap) std::memcpy(json, j.c_str(), j.size() + 1);
   return j.size();
+}
+
+// K6: host-link (PCIe) check (host_link.hpp; host side in host_link_plan.hpp).
+// `host` is pinned, device-mapped host memory (hipHostMalloc, hipHostRegister,
+// a pinned torch tensor): each entry point resolves it with
+// hipHostGetDevicePointer and returns hipErrorInvalidValue for memory that is
+// not mapped, a size or base that is no 16-byte multiple, or an unknown
+// pattern. blocks <= 0: ntm_host_link_default_blocks(pull). The _ex entry points
+// take the sweep's knobs (unroll 1 / 2 / 4 / 8, nt = nontemporal accesses;
+// tools/host_link_rates.py); the plain ones run the measured defaults.
+namespace {
+namespace hl = ntm::hostlink;
+
+// The device's view of [host, host + bytes), or null when either end is not mapped.
+void* mapped(const void* host, size_t bytes) {
+  void *d0 = nullptr, *d1 = nullptr;
+  if (!host || bytes == 0) return nullptr;
+  if (hipHostGetDevicePointer(&d0, const_cast<void*>(host), 0) != hipSuccess ||
+      hipHostGetDevicePointer(&d1, (char*)const_cast<void*>(host) + (bytes - 1), 0) != hipSuccess ||
+      !d0 || (char*)d1 - (char*)d0 != (ptrdiff_t)(bytes - 1)) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return d0;
+}
+bool link_args_ok(const void* host, size_t bytes, unsigned long long base_bytes, int pattern,
+                  int blocks) {
+  return host && (uintptr_t)host % 16 == 0 && bytes % 16 == 0 && base_bytes % 16 == 0 &&
+         blocks <= hl::kMaxBlocks &&
+         (pattern == ntm::hbm::kPatternAddr || pattern == ntm::hbm::kPatternHash);
+}
+inline unsigned link_grid(int blocks, bool pull) {
+  return (unsigned)(blocks > 0 ? blocks : pull ? hl::kPullBlocks : hl::kPushBlocks);
+}
+
+template <int PAT, int U, bool NT>
+void push_launch(void* d, size_t n4, uint64_t bw, uint64_t seed, uint32_t inv, unsigned g,
+                 hipStream_t s) {
+  hipLaunchKernelGGL((hl::host_link_push_kernel<PAT, U, NT>), dim3(g), dim3(256), 0, s,
+                     (hl::u32x4*)d, n4, bw, seed, inv);
+}
+template <int PAT, int U, bool NT>
+void pull_launch(const void* d, size_t n4, uint64_t bw, uint64_t seed, uint32_t inv, void* dst,
+                 void* result, unsigned g, hipStream_t s) {
+  if (dst)
+    hipLaunchKernelGGL((hl::host_link_pull_kernel<PAT, U, true, NT>), dim3(g), dim3(256), 0, s,
+                       (const hl::u32x4*)d, n4, bw, seed, inv, (hl::u32x4*)dst,
+                       (hl::PatternResult*)result);
+  else
+    hipLaunchKernelGGL((hl::host_link_pull_kernel<PAT, U, false, NT>), dim3(g), dim3(256), 0, s,
+                       (const hl::u32x4*)d, n4, bw, seed, inv, (hl::u32x4*)nullptr,
+                       (hl::PatternResult*)result);
+}
+// f(<PAT>, <U>, <NT>) as integral constants; false for knobs outside the sweep
+template <typename F>
+bool with_link_knobs(int pattern, int unroll, int nt, F&& f) {
+  auto pat = [&](auto u, auto n) {
+    if (pattern == ntm::hbm::kPatternAddr) f(std::integral_constant<int, ntm::hbm::kPatternAddr>{}, u, n);
+    else f(std::integral_constant<int, ntm::hbm::kPatternHash>{}, u, n);
+  };
+  auto un = [&](auto n) -> bool {
+    switch (unroll) {
+      case 1: pat(std::integral_constant<int, 1>{}, n); return true;
+      case 2: pat(std::integral_constant<int, 2>{}, n); return true;
+      case 4: pat(std::integral_constant<int, 4>{}, n); return true;
+      case 8: pat(std::integral_constant<int, 8>{}, n); return true;
+      default: return false;
+    }
+  };
+  return nt ? un(std::true_type{}) : un(std::false_type{});
+}
+}  // namespace
+
+// blocks of the push (pull != 0: pull) kernel when the caller passes blocks <= 0
+NTM_API int ntm_host_link_default_blocks(int pull) { return pull ? hl::kPullBlocks : hl::kPushBlocks; }
+// bytes one block moves per loop trip in the default push (pull != 0: pull) build
+NTM_API int ntm_host_link_tile_bytes(int pull) {
+  return 256 * 16 * (pull ? hl::kPullUnroll : hl::kPushUnroll);
+}
+
+NTM_API int ntm_host_link_push_ex(void* host, size_t bytes, unsigned long long base_bytes,
+                                  int pattern, unsigned long long seed, int invert, int blocks,
+                                  int unroll, int nt, void* stream) {
+  if (!link_args_ok(host, bytes, base_bytes, pattern, blocks)) return (int)hipErrorInvalidValue;
+  if (bytes == 0) return 0;
+  void* d = mapped(host, bytes);
+  if (!d) return (int)hipErrorInvalidValue;
+  const uint32_t inv = invert ? ~0u : 0u;
+  const bool ok = with_link_knobs(pattern, unroll, nt, [&](auto p, auto u, auto n) {
+    push_launch<decltype(p)::value, decltype(u)::value, decltype(n)::value>(
+        d, bytes / 16, base_bytes / 4, seed, inv, link_grid(blocks, false), S(stream));
+  });
+  return ok ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
+}
+
+NTM_API int ntm_host_link_push(void* host, size_t bytes, unsigned long long base_bytes,
+                               int pattern, unsigned long long seed, int invert, int blocks,
+                               void* stream) {
+  return ntm_host_link_push_ex(host, bytes, base_bytes, pattern, seed, invert, blocks,
+                               hl::kPushUnroll, hl::kPushNontemporal, stream);
+}
+
+// `result`: one initialised ntm::hbm::PatternResult in device memory (as for
+// ntm_hbm_pattern_verify); `dst`: null, or `bytes` of HBM that receive what was read.
+NTM_API int ntm_host_link_pull_ex(const void* host, size_t bytes, unsigned long long base_bytes,
+                                  int pattern, unsigned long long seed, int invert, void* dst,
+                                  int blocks, int unroll, int nt, void* result, void* stream) {
+  if (!link_args_ok(host, bytes, base_bytes, pattern, blocks) || !result ||
+      (uintptr_t)result % 64 || (uintptr_t)dst % 16)
+    return (int)hipErrorInvalidValue;
+  if (bytes == 0) return 0;
+  const void* d = mapped(host, bytes);
+  if (!d) return (int)hipErrorInvalidValue;
+  const uint32_t inv = invert ? ~0u : 0u;
+  const bool ok = with_link_knobs(pattern, unroll, nt, [&](auto p, auto u, auto n) {
+    pull_launch<decltype(p)::value, decltype(u)::value, decltype(n)::value>(
+        d, bytes / 16, base_bytes / 4, seed, inv, dst, result, link_grid(blocks, true), S(stream));
+  });
+  return ok ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
+}
+
+NTM_API int ntm_host_link_pull(const void* host, size_t bytes, unsigned long long base_bytes,
+                               int pattern, unsigned long long seed, int invert, void* dst,
+                               int blocks, void* result, void* stream) {
+  return ntm_host_link_pull_ex(host, bytes, base_bytes, pattern, seed, invert, dst, blocks,
+                               hl::kPullUnroll, hl::kPullNontemporal, result, stream);
+}
+
+// `host`: nslots slots of 64 bytes (host_link_plan.hpp chase_fill); `out`: 3 u64 of
+// device memory (final index, wall_clock64 ticks, hops done).
+NTM_API int ntm_host_link_chase(const void* host, unsigned long long nslots,
+                                unsigned long long start, unsigned hops, void* out, void* stream) {
+  if (!host || (uintptr_t)host % 8 || nslots == 0 || nslots > (1ull << 32) || start >= nslots ||
+      hops == 0 || !out || (uintptr_t)out % 8)
+    return (int)hipErrorInvalidValue;
+  const void* d = mapped(host, (size_t)nslots * hl::kChaseSlotBytes);
+  if (!d) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(hl::host_link_chase_kernel, dim3(1), dim3(64), 0, S(stream),
+                     (const unsigned long long*)d, nslots, start, hops, (unsigned long long*)out);
+  return (int)hipGetLastError();
+}
+
+// wall_clock64() ticks per millisecond on `device` (0 on an error).
+NTM_API int ntm_host_link_clock_khz(int device) {
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeWallClockRate, device) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return v;
 }

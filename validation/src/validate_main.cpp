@@ -11,6 +11,9 @@
 //       (--hbm-test-gb; ntm/hbm_pattern.hpp)
 //   K5  per-CU compute sweep that names a bad CU, off by default
 //       (--cu-sweep; ntm/cu_sweep.hpp)
+//   K6  host-link (PCIe) check: verified transfers both ways through pinned
+//       host memory, rate and read latency, off by default
+//       (--host-link-mib; ntm/host_link.hpp)
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL
@@ -44,6 +47,7 @@
 #include "ntm/common.hpp"
 #include "ntm/cu_sweep_plan.hpp"
 #include "ntm/hbm_test_plan.hpp"
+#include "ntm/host_link_plan.hpp"
 
 namespace ntm {
 namespace xgmi {
@@ -88,6 +92,11 @@ int ntm_hbm_pattern_verify(void*, size_t, unsigned long long, int, unsigned long
 int ntm_hbm_pattern_result_bytes();
 int ntm_cu_sweep_launch(void*, const void*, unsigned, int, size_t, unsigned, unsigned, int, void*);
 int ntm_cu_sweep_max_lds_bytes(int);
+int ntm_host_link_push(void*, size_t, unsigned long long, int, unsigned long long, int, int, void*);
+int ntm_host_link_pull(const void*, size_t, unsigned long long, int, unsigned long long, int, void*,
+                       int, void*, void*);
+int ntm_host_link_chase(const void*, unsigned long long, unsigned long long, unsigned, void*, void*);
+int ntm_host_link_clock_khz(int);
 }
 
 namespace {
@@ -126,6 +135,8 @@ struct Opts {
   int hbm_test_passes = 1;
   bool cu_sweep = false;        // K5: off unless asked for
   int cu_sweep_iters = 16;      // rounds per workgroup (profiles/cu_sweep/README.md)
+  long host_link_mib = 0;       // K6: 0 = off; MiB of pinned host memory per GPU
+  double host_link_floor_gbps = 0;  // per direction, 0 = report only
   long allreduce_max_mib = 8192;  // 8 GiB, capped by free HBM
   bool xgmi = true;
   int xgmi_sim = 0;             // C2 with N simulated ranks on GPU 0 (one-GPU test path)
@@ -159,6 +170,7 @@ void usage() {
                "       [--tflops-floor TF] [--min-hbm-gb GB] [--hbm-floor-gbps GBps]\n"
                "       [--hbm-test-gb GB] [--hbm-test-passes P]\n"
                "       [--cu-sweep] [--cu-sweep-iters N]\n"
+               "       [--host-link-mib MiB] [--host-link-floor-gbps GBps]\n"
                "       [--allreduce-max-mib MiB] [--rccl | --no-rccl] [--no-xgmi] [--xgmi-sim N]\n"
                "       [--settle-s S] [--no-fp8] [--fp8-tflops-floor TF]\n"
                "       [--no-p2p] [--p2p-mib MiB] [--p2p-floor-gbps GBps] [--p2p-loopback]\n"
@@ -170,7 +182,7 @@ void usage() {
                "       [--pushgateway http://host:port]\n"
                "fault-inject (also env NTM_FAULT_INJECT): corrupt_gemm | corrupt_abft |\n"
                "       corrupt_fp8 | corrupt_fp8_abft | corrupt_p2p | corrupt_allreduce |\n"
-               "       corrupt_hbm | bad_cu | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
+               "       corrupt_hbm | bad_cu | corrupt_host_link | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
                "       launch claims a wrong XCD; corrupt_hbm: one bit of the pattern test's\n"
                "       last chunk, needs --hbm-test-gb) to prove detection\n"
                "hbm-test-gb: K4, write / read back / compare an address pattern and a hash\n"
@@ -180,7 +192,13 @@ void usage() {
                "       per CU and launch, up to 8 launches until every CU ran one); a failure\n"
                "       names xcd, se, sh, cu and simd; cu-sweep-iters: rounds per workgroup\n"
                "       (default 16). fault-inject bad_cu (needs --cu-sweep): the workgroups on one\n"
-               "       CU of the LAST GPU flip one bit of a computed value\n");
+               "       CU of the LAST GPU flip one bit of a computed value\n"
+               "host-link-mib: K6, the GPU writes a hash pattern into MiB of pinned host memory,\n"
+               "       reads it back over the host link (PCIe) and compares on the device; also\n"
+               "       both at once, hipMemcpyAsync both ways and the read latency; 0 = off\n"
+               "       (default). host-link-floor-gbps: fail when a direction's faster path (kernel or\n"
+               "       hipMemcpyAsync) is below GBps (0 = report only). fault-inject corrupt_host_link\n"
+               "       (needs --host-link-mib): the host flips one bit of the LAST GPU's pinned buffer\n");
 }
 
 bool parse(int argc, char** argv, Opts& o) {
@@ -203,6 +221,8 @@ bool parse(int argc, char** argv, Opts& o) {
     else if (a == "--hbm-test-gb") { if (!(v = next(a.c_str()))) return false; o.hbm_test_gb = std::atof(v); }
     else if (a == "--cu-sweep") o.cu_sweep = true;
     else if (a == "--cu-sweep-iters") { if (!(v = next(a.c_str()))) return false; o.cu_sweep_iters = std::atoi(v); }
+    else if (a == "--host-link-mib") { if (!(v = next(a.c_str()))) return false; o.host_link_mib = std::atol(v); }
+    else if (a == "--host-link-floor-gbps") { if (!(v = next(a.c_str()))) return false; o.host_link_floor_gbps = std::atof(v); }
     else if (a == "--hbm-test-passes") { if (!(v = next(a.c_str()))) return false; o.hbm_test_passes = std::atoi(v); }
     else if (a == "--allreduce-max-mib") { if (!(v = next(a.c_str()))) return false; o.allreduce_max_mib = std::atol(v); }
     else if (a == "--no-xgmi") o.xgmi = false;
@@ -236,7 +256,8 @@ bool parse(int argc, char** argv, Opts& o) {
   return o.size > 0 && o.iters > 0 && o.p2p_mib > 0 && o.allreduce_max_mib > 0 &&
          o.xgmi_sim >= 0 && o.xgmi_sim <= ntm::xgmi::kMaxRanks && o.settle_s >= 0 &&
          o.hbm_test_passes >= 1 && std::isfinite(o.hbm_test_gb) && o.cu_sweep_iters >= 1 &&
-         o.cu_sweep_iters <= ntm::cus::kMaxIters;
+         o.cu_sweep_iters <= ntm::cus::kMaxIters && o.host_link_mib >= 0 &&
+         o.host_link_mib <= (1l << 20) && o.host_link_floor_gbps >= 0;
 }
 
 // ------------------------------------------------------------ JSON helpers
@@ -342,6 +363,16 @@ struct GpuResult {
   int cu_sweep_lds_bytes = 0;
   double cu_sweep_s = 0;
   std::string cu_sweep_failure;  // empty = clean
+  // K6 (only with --host-link-mib)
+  bool host_link_ran = false;
+  long host_link_mib = 0;
+  double host_link_h2d_gbps = 0, host_link_d2h_gbps = 0;            // pull / push kernels
+  double host_link_h2d_copy_gbps = 0, host_link_d2h_copy_gbps = 0;  // hipMemcpyAsync
+  double host_link_duplex_gbps = 0, host_link_latency_us = 0;
+  unsigned long long host_link_bad_words = 0, host_link_bad_bits = 0;
+  ntm::hostlink::LinkState host_link_pcie;
+  double host_link_s = 0, host_link_pin_s = 0, host_link_xfer_s = 0, host_link_free_s = 0;
+  std::vector<std::string> host_link_failures;  // empty = clean
 };
 
 // The split-mode self-check shape: 48 x 5 of 192x256 tiles, half a round on
@@ -550,6 +581,177 @@ bool run_cu_sweep(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r
   CK(hipFree(dexp));
   CK(hipFree(drec));
   r.cu_sweep_s = std::chrono::duration<double>(Clock::now() - t_begin).count();
+  return true;
+}
+
+// ---- K6: host-link (PCIe) check (ntm/host_link.hpp, host side in ntm/host_link_plan.hpp).
+// One pinned buffer and one HBM buffer of --host-link-mib: push the HASH pattern
+// (device->host), pull and verify on the device (host->device), both at once on
+// two streams over the two halves, hipMemcpyAsync both ways on the same buffers
+// (the path frameworks use: the reference for the kernels' rate), then the
+// pointer chase. Rates are medians of 3, timed with events. The healthy path does
+// no CPU work on the data; on a mismatch the host re-checks the pinned buffer to
+// say which direction went wrong. corrupt_host_link: the host flips one bit of
+// the pinned buffer between push and pull.
+bool run_host_link(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r) {
+  namespace hl = ntm::hostlink;
+  namespace hb = ntm::hbm;
+  const auto t_begin = Clock::now();
+  auto since = [](Clock::time_point t0) {
+    return std::chrono::duration<double>(Clock::now() - t0).count();
+  };
+  auto median3 = [](double a, double b, double c) {
+    return std::max(std::min(a, b), std::min(std::max(a, b), c));
+  };
+  const std::string d = "gpu" + std::to_string(dev) + ": ";
+  const size_t bytes = (size_t)o.host_link_mib << 20;
+  const size_t half = bytes / 2;  // a multiple of 16: bytes is a multiple of 1 MiB
+  constexpr int kPat = hb::kPatternHash;
+  const unsigned long long seed = 0x4B36ull + (unsigned)dev;
+  r.host_link_ran = true;
+  r.host_link_mib = o.host_link_mib;
+  char bus[32] = {0};
+  if (hipDeviceGetPCIBusId(bus, sizeof bus, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    bus[0] = 0;
+  }
+  void *hbuf = nullptr, *dbuf = nullptr;
+  if (hipHostMalloc(&hbuf, bytes, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();  // no pinned memory (RLIMIT_MEMLOCK, host RAM): a verdict, no HIP failure
+    r.host_link_failures.push_back(d + "host link: cannot pin " + std::to_string(o.host_link_mib) +
+                                   " MiB of host memory");
+    r.host_link_s = since(t_begin);
+    return true;
+  }
+  r.host_link_pin_s = since(t_begin);
+  const auto t_xfer = Clock::now();
+  hb::PatternResult *dres = nullptr, hres, init;
+  unsigned long long* dchase = nullptr;
+  hb::pattern_result_init(init);
+  CK(hipMalloc(&dbuf, bytes));
+  CK(hipMalloc(&dres, sizeof(hb::PatternResult)));
+  CK(hipMalloc(&dchase, 3 * sizeof(unsigned long long)));
+  hipStream_t s2;
+  hipEvent_t e0, e1;
+  CK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+  CK(hipEventCreate(&e0));
+  CK(hipEventCreate(&e1));
+  float ms = 0;
+  double t[3];
+  // device->host; the link state is read while the last push is in flight (AMD GPUs
+  // drop the link speed at idle)
+  for (int i = 0; i < 3; ++i) {
+    CK(hipEventRecord(e0, s));
+    CK(ntm_host_link_push(hbuf, bytes, 0, kPat, seed, 0, 0, s));
+    CK(hipEventRecord(e1, s));
+    if (i == 2 && bus[0]) r.host_link_pcie = hl::read_link_state("/sys", bus);
+    CK(hipEventSynchronize(e1));
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    t[i] = ms;
+  }
+  r.host_link_d2h_gbps = bytes / (median3(t[0], t[1], t[2]) * 1e-3) / 1e9;
+  if (last && o.fault == "corrupt_host_link")
+    ((uint32_t*)hbuf)[((bytes / 2) & ~(size_t)15) / 4 + 1] ^= 1u << 13;
+  // host->device, compared on the device; the first pull that finds a bad word ends the stage
+  bool clean = true;
+  int pulls = 0;
+  for (int i = 0; i < 3 && clean; ++i) {
+    CK(hipMemcpyAsync(dres, &init, sizeof init, hipMemcpyHostToDevice, s));
+    CK(hipEventRecord(e0, s));
+    CK(ntm_host_link_pull(hbuf, bytes, 0, kPat, seed, 0, nullptr, 0, dres, s));
+    CK(hipEventRecord(e1, s));
+    CK(hipMemcpyAsync(&hres, dres, sizeof hres, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    t[pulls++] = ms;
+    if (hres.bad_words) {
+      clean = false;
+      r.host_link_bad_words = hres.bad_words;
+      r.host_link_bad_bits = hres.bad_bits_or;
+      // which direction: is the pinned buffer itself wrong?
+      hb::PatternResult host_res;
+      const bool host_bad = hl::host_check(hbuf, bytes, 0, kPat, seed, false, host_res) != 0;
+      r.host_link_failures.push_back(
+          hl::data_failure_message(dev, host_bad ? hl::kDirPush : hl::kDirPull, host_bad ? host_res : hres));
+    }
+  }
+  // a stage cut short reports its first pull
+  r.host_link_h2d_gbps = bytes / ((pulls == 3 ? median3(t[0], t[1], t[2]) : t[0]) * 1e-3) / 1e9;
+  if (clean) {
+    // duplex: push into the first half, pull from the second, wall time of both
+    CK(hipMemcpyAsync(dres, &init, sizeof init, hipMemcpyHostToDevice, s2));
+    CK(hipStreamSynchronize(s2));
+    for (int i = 0; i < 3; ++i) {
+      CK(hipStreamSynchronize(s));
+      const auto t0 = Clock::now();
+      CK(ntm_host_link_push(hbuf, half, 0, kPat, seed, 0, 0, s));
+      CK(ntm_host_link_pull((char*)hbuf + half, half, half, kPat, seed, 0, nullptr, 0, dres, s2));
+      CK(hipStreamSynchronize(s));
+      CK(hipStreamSynchronize(s2));
+      t[i] = since(t0) * 1e3;
+    }
+    r.host_link_duplex_gbps = 2.0 * half / (median3(t[0], t[1], t[2]) * 1e-3) / 1e9;
+    CK(hipMemcpy(&hres, dres, sizeof hres, hipMemcpyDeviceToHost));
+    if (hres.bad_words) {
+      r.host_link_bad_words = hres.bad_words;
+      r.host_link_bad_bits = hres.bad_bits_or;
+      r.host_link_failures.push_back(hl::data_failure_message(dev, "duplex host->device read", hres));
+    }
+    // hipMemcpyAsync on the same buffers, both ways
+    for (int dir = 0; dir < 2; ++dir) {
+      for (int i = 0; i < 3; ++i) {
+        CK(hipEventRecord(e0, s));
+        if (dir == 0) CK(hipMemcpyAsync(dbuf, hbuf, bytes, hipMemcpyHostToDevice, s));
+        else CK(hipMemcpyAsync(hbuf, dbuf, bytes, hipMemcpyDeviceToHost, s));
+        CK(hipEventRecord(e1, s));
+        CK(hipEventSynchronize(e1));
+        CK(hipEventElapsedTime(&ms, e0, e1));
+        t[i] = ms;
+      }
+      (dir == 0 ? r.host_link_h2d_copy_gbps : r.host_link_d2h_copy_gbps) =
+          bytes / (median3(t[0], t[1], t[2]) * 1e-3) / 1e9;
+    }
+    // read round trip: 4096 dependent loads through a 1024-slot cycle in host memory
+    const size_t chase_bytes = (size_t)hl::kChaseSlots * hl::kChaseSlotBytes;
+    const int khz = ntm_host_link_clock_khz(dev);
+    if (bytes >= chase_bytes && khz > 0) {
+      const std::vector<uint32_t> next = hl::chase_permutation(hl::kChaseSlots, seed);
+      hl::chase_fill(hbuf, next);
+      unsigned long long out[3] = {0, 0, 0};
+      CK(ntm_host_link_chase(hbuf, hl::kChaseSlots, 0, hl::kChaseHops, dchase, s));
+      CK(hipMemcpyAsync(out, dchase, sizeof out, hipMemcpyDeviceToHost, s));
+      CK(hipStreamSynchronize(s));
+      const uint32_t want = hl::chase_walk(next, 0, hl::kChaseHops);
+      if (out[0] != want || out[2] != hl::kChaseHops)
+        r.host_link_failures.push_back(d + "host link chase ended at slot " + std::to_string(out[0]) +
+                                       " after " + std::to_string(out[2]) + " hops, expected slot " +
+                                       std::to_string(want) + " after " + std::to_string(hl::kChaseHops));
+      else
+        r.host_link_latency_us = (double)out[1] / khz * 1e3 / hl::kChaseHops;
+    }
+    // the floor: per direction, on the faster of kernel and hipMemcpyAsync (a degraded link caps both)
+    if (o.host_link_floor_gbps > 0) {
+      const double h2d = std::max(r.host_link_h2d_gbps, r.host_link_h2d_copy_gbps);
+      const double d2h = std::max(r.host_link_d2h_gbps, r.host_link_d2h_copy_gbps);
+      if (h2d < o.host_link_floor_gbps)
+        r.host_link_failures.push_back(
+            hl::rate_failure_message(dev, "host->device", h2d, o.host_link_floor_gbps, r.host_link_pcie));
+      if (d2h < o.host_link_floor_gbps)
+        r.host_link_failures.push_back(
+            hl::rate_failure_message(dev, "device->host", d2h, o.host_link_floor_gbps, r.host_link_pcie));
+    }
+  }
+  r.host_link_xfer_s = since(t_xfer);
+  const auto t_free = Clock::now();
+  CK(hipEventDestroy(e0));
+  CK(hipEventDestroy(e1));
+  CK(hipStreamDestroy(s2));
+  CK(hipFree(dchase));
+  CK(hipFree(dres));
+  CK(hipFree(dbuf));
+  CK(hipHostFree(hbuf));
+  r.host_link_free_s = since(t_free);
+  r.host_link_s = since(t_begin);
   return true;
 }
 
@@ -790,6 +992,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   CK(hipFree(dst));
   if (o.hbm_test_gb != 0 && !run_hbm_test(dev, last, o, s, r)) return false;
   if (o.cu_sweep && !run_cu_sweep(dev, last, o, s, r)) return false;
+  if (o.host_link_mib > 0 && !run_host_link(dev, last, o, s, r)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));
@@ -1483,6 +1686,7 @@ int main(int argc, char** argv) {
     if (!r.hbm_copy_ok) fail(d + "HBM copy mismatch");
     if (!r.hbm_test_failure.empty()) fail(r.hbm_test_failure);
     if (!r.cu_sweep_failure.empty()) fail(r.cu_sweep_failure);
+    for (auto& f : r.host_link_failures) fail(f);
     if (o.hbm_floor_gbps > 0 && r.hbm_copy_gbps < o.hbm_floor_gbps)
       fail(d + "HBM copy " + jnum(r.hbm_copy_gbps) + " GB/s below floor");
   }
@@ -1565,6 +1769,21 @@ int main(int argc, char** argv) {
         if (r.cu_sweep_ran)
           p << "amdgpu_validate_cu_sweep_bad_cus{gpu=\"" << r.device << "\"} " << r.cu_sweep.bad_cus.size() << "\n";
     }
+    if (o.host_link_mib > 0) {
+      auto gauge = [&](const char* name, const char* help, auto value) {
+        p << "# HELP amdgpu_validate_host_link_" << name << " " << help << "\n"
+          << "# TYPE amdgpu_validate_host_link_" << name << " gauge\n";
+        for (auto& r : res)
+          if (r.host_link_ran)
+            p << "amdgpu_validate_host_link_" << name << "{gpu=\"" << r.device << "\"} " << value(r) << "\n";
+      };
+      gauge("h2d_gbps", "Host-to-device rate over the host link (faster of kernel and hipMemcpyAsync).",
+            [](const GpuResult& r) { return jnum(std::max(r.host_link_h2d_gbps, r.host_link_h2d_copy_gbps)); });
+      gauge("d2h_gbps", "Device-to-host rate over the host link (faster of kernel and hipMemcpyAsync).",
+            [](const GpuResult& r) { return jnum(std::max(r.host_link_d2h_gbps, r.host_link_d2h_copy_gbps)); });
+      gauge("bad_words", "8-byte words that crossed the host link wrong.",
+            [](const GpuResult& r) { return std::to_string(r.host_link_bad_words); });
+    }
     if (!rccl_rows.empty() || !xgmi_rows.empty())
       p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
         << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(peak_rccl) << "\n"
@@ -1633,6 +1852,21 @@ int main(int argc, char** argv) {
             ",\"cu_sweep_bad_cus\":" + ntm::cus::bad_cus_json(r.cu_sweep) +
             ",\"cu_sweep_lds_bytes\":" + std::to_string(r.cu_sweep_lds_bytes) +
             ",\"cu_sweep_s\":" + jnum(r.cu_sweep_s);
+    if (r.host_link_ran)
+      js += ",\"host_link_mib\":" + std::to_string(r.host_link_mib) +
+            ",\"host_link_h2d_GBps\":" + jnum(r.host_link_h2d_gbps) +
+            ",\"host_link_d2h_GBps\":" + jnum(r.host_link_d2h_gbps) +
+            ",\"host_link_h2d_copy_GBps\":" + jnum(r.host_link_h2d_copy_gbps) +
+            ",\"host_link_d2h_copy_GBps\":" + jnum(r.host_link_d2h_copy_gbps) +
+            ",\"host_link_duplex_GBps\":" + jnum(r.host_link_duplex_gbps) +
+            ",\"host_link_read_latency_us\":" + jnum(r.host_link_latency_us) +
+            ",\"host_link_bad_words\":" + std::to_string(r.host_link_bad_words) +
+            ",\"host_link_bad_bits\":" + std::to_string(r.host_link_bad_bits) +
+            ",\"host_link_pcie\":" + ntm::hostlink::link_json(r.host_link_pcie) +
+            ",\"host_link_s\":" + jnum(r.host_link_s) +
+            ",\"host_link_pin_s\":" + jnum(r.host_link_pin_s) +
+            ",\"host_link_transfer_s\":" + jnum(r.host_link_xfer_s) +
+            ",\"host_link_free_s\":" + jnum(r.host_link_free_s);
     js += "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(rccl_rows);
