@@ -58,6 +58,8 @@ locals {
     var.validation_host_link_mib != 0 && var.validation_host_link_floor_gbps != 0 ? [
       "--host-link-floor-gbps", tostring(var.validation_host_link_floor_gbps),
     ] : [],
+    # K7: the MX block-scaled matrix check (MXFP8 / MXFP6 / MXFP4), off unless asked for
+    var.validation_mx_check ? ["--mx-check"] : [],
     # one-line verdict surfaced as the pod's termination message
     ["--termination-log", "/dev/termination-log"],
   )

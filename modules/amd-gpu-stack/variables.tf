@@ -340,6 +340,12 @@ variable "validation_host_link_floor_gbps" {
   }
 }
 
+variable "validation_mx_check" {
+  type        = bool
+  default     = false
+  description = "Run the Job's MX block-scaled matrix check (K7): GEMMs on the scaled f8f6f4 matrix instruction with real E8M0 scales per 32-element block - a decode sweep of e4m3, e5m2, e2m3, e3m2 and e2m1 against an integer table, dense MXFP6 (e2m3) and dense MXFP4 (e2m1, 4096^3) against a reference kernel that uses no matrix core - every element compared bitwise, then the MXFP4 rate (reported only). A wrong element fails the Job; the message names the GPU, the format, row, column, expected and got. Measurements: profiles/mx/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

@@ -14,6 +14,10 @@ K5 ``cu_sweep``, ``cu_sweep_decode``, ``cu_sweep_summarize`` - known-answer LDS 
    MFMA sub-tests per workgroup, tied to the CU that ran them.
 K6 ``host_link_push``, ``host_link_pull``, ``host_link_chase`` - the same pattern written to and
    read from pinned host memory over the host link (PCIe), and its read round-trip latency.
+K7 ``mx_gemm``, ``mx_reference_gpu``, ``mx_compare`` - a block-scaled GEMM in the MX formats
+   (e4m3, e5m2, e2m3, e3m2, e2m1 with E8M0 scales) on the scaled f8f6f4 matrix instruction, a
+   reference without matrix cores and a bitwise compare; ``mx_pack``, ``mx_unpack``,
+   ``mx_make_inputs``, ``mx_dense_exact`` - the host side (numpy, ``ops.mx``).
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -68,6 +72,10 @@ from .kernels import (  # noqa: F401
     host_link_pull,
     host_link_push,
     host_link_tile_bytes,
+    MxCompareReport,
+    mx_compare,
+    mx_gemm,
+    mx_reference_gpu,
     CU_SWEEP_SUBTESTS,
     cu_sweep,
     cu_sweep_decode,
@@ -75,4 +83,14 @@ from .kernels import (  # noqa: F401
     cu_sweep_record_dtype,
     cu_sweep_summarize,
     verify_bf16,
+)
+from .mx import (  # noqa: F401
+    MX_FORMATS,
+    mx_dense_exact,
+    mx_make_inputs,
+    mx_matmul_bits,
+    mx_max_spread,
+    mx_pack,
+    mx_shape_ok,
+    mx_unpack,
 )

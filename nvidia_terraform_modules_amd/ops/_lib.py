@@ -113,6 +113,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "ntm_host_link_chase": ([c_vp, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_vp,
                                  c_vp], c_int),
         "ntm_host_link_clock_khz": ([c_int], c_int),
+        "ntm_mx_shape_ok": ([c_int, c_int, c_int], c_int),
+        "ntm_mx_gemm": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+        "ntm_mx_reference": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+        "ntm_mx_compare": ([c_vp, c_vp, c_size, c_vp, c_vp], c_int),
+        "ntm_mx_mismatch_bytes": ([], c_int),
         "ntm_cu_sweep_record_bytes": ([], c_int),
         "ntm_cu_sweep_expected_bytes": ([c_int], c_size),
         "ntm_cu_sweep_expected": ([c_int, ctypes.c_uint, c_vp, c_size], c_int),
@@ -158,6 +163,7 @@ def _declare_experimental(lib: ctypes.CDLL) -> None:
         "ntm_gemm_bf16_stamp": (
             [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp], c_int),
         "ntm_mfma_f8_probe": ([c_vp, c_vp, c_vp, c_vp], c_int),
+        "ntm_mx_mfma_probe": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp], c_int),
         "ntm_mfma_rate": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_mfma_toggle": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_dma_probe": ([c_int, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),

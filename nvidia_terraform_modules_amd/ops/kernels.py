@@ -11,6 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from ._lib import check, lib, lib_experimental, stream_handle
+from .mx import MX_BLOCK, mx_bits, mx_format_id, mx_shape_ok
 
 BM = BN = 256
 BK = 64
@@ -897,6 +898,100 @@ def host_link_chase(host: torch.Tensor, hops: int, start: int = 0) -> tuple[int,
     if done != hops:
         raise RuntimeError(f"host_link_chase read {final}, not a slot index, after {done} hops")
     return final, ticks / khz * 1e6 / hops
+
+
+# K7: MX block-scaled matrix check (validation/include/ntm/mx_gemm.hpp, mx_plan.hpp). The
+# host side (formats, packing, generators, bound, exact reference) is numpy: ops/mx.py.
+@dataclass
+class MxCompareReport:
+    count: int                 # 32-bit words that differ
+    first_index: int | None    # smallest flat index of one
+    expected: int | None       # the words at first_index
+    got: int | None
+
+    @property
+    def ok(self) -> bool:
+        return self.count == 0
+
+    def as_dict(self) -> dict:
+        return {"count": self.count, "first_index": self.first_index, "expected": self.expected,
+                "got": self.got, "ok": self.ok}
+
+
+def mx_check_args(a, b, sa, sb, fmt, out=None, need_cuda: bool = True) -> tuple[int, int, int, int]:
+    """(format code, M, N, K) of one MX product; ValueError unless a / b / sa / sb are
+    contiguous uint8 matrices (on one GPU when ``need_cuda``) whose shapes agree, with M, N
+    and K multiples of 128, and ``out`` (if given) a contiguous fp32 [M, N] beside them."""
+    f = mx_format_id(fmt)
+    bits = mx_bits(f)
+    for name, t in (("a", a), ("b", b), ("sa", sa), ("sb", sb)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"MX check: {name} must be a contiguous 2-D uint8 tensor")
+        if need_cuda and not t.is_cuda:
+            raise ValueError("MX check needs GPU tensors")
+        if t.device != a.device:
+            raise ValueError("MX check: all tensors must be on one device")
+    M, N = a.shape[0], b.shape[0]
+    K = a.shape[1] * 8 // bits
+    if (a.shape[1] * 8) % bits or b.shape[1] != a.shape[1] or not mx_shape_ok(M, N, K):
+        raise ValueError("MX check needs a [M, K*bits/8], b [N, K*bits/8] with M, N, K multiples of 128")
+    if tuple(sa.shape) != (M, K // MX_BLOCK) or tuple(sb.shape) != (N, K // MX_BLOCK):
+        raise ValueError("MX check needs sa [M, K/32] and sb [N, K/32]")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32
+                            or tuple(out.shape) != (M, N) or not out.is_contiguous()
+                            or out.device != a.device):
+        raise ValueError("MX check: out must be a contiguous fp32 [M, N] tensor on the operands' device")
+    return f, M, N, K
+
+
+def _mx_product(entry: str, a, b, sa, sb, fmt, out):
+    f, M, N, K = mx_check_args(a, b, sa, sb, fmt, out)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = getattr(lib(), entry)(f, a.data_ptr(), b.data_ptr(), sa.data_ptr(), sb.data_ptr(),
+                                   out.data_ptr(), M, N, K, stream_handle())
+    check(rc, entry)
+    return out
+
+
+def mx_gemm(a: torch.Tensor, b: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor, fmt,
+            out: torch.Tensor | None = None) -> torch.Tensor:
+    """K7: C [M, N] fp32 = A @ B.T on the block-scaled f8f6f4 matrix instruction. ``a`` / ``b``:
+    packed uint8 rows of format ``fmt`` (``mx_pack``), ``sa`` / ``sb``: E8M0 scale bytes
+    [rows, K/32]. M, N and K must be multiples of 128. Stream-ordered."""
+    return _mx_product("ntm_mx_gemm", a, b, sa, sb, fmt, out)
+
+
+def mx_reference_gpu(a: torch.Tensor, b: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor, fmt,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """K7: the same product without the matrix cores (integer decode, ldexpf, an fp32 FMA
+    chain in k order); exact under ``mx_dense_exact``. Stream-ordered."""
+    return _mx_product("ntm_mx_reference", a, b, sa, sb, fmt, out)
+
+
+def mx_compare(expected: torch.Tensor, got: torch.Tensor) -> MxCompareReport:
+    """K7: bitwise compare of two GPU tensors of 32-bit elements on the device
+    (synchronises)."""
+    for t in (expected, got):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("mx_compare needs GPU tensors")
+        if t.element_size() != 4 or not t.is_contiguous():
+            raise ValueError("mx_compare needs contiguous tensors of 32-bit elements")
+    if expected.numel() != got.numel() or expected.device != got.device:
+        raise ValueError("mx_compare needs two tensors of one size on one device")
+    res = torch.zeros(lib().ntm_mx_mismatch_bytes() // 8, dtype=torch.int64, device=got.device)
+    res[1] = -1                                     # first_index: all ones
+    with torch.cuda.device(got.device):
+        rc = lib().ntm_mx_compare(expected.data_ptr(), got.data_ptr(), expected.numel(),
+                                  res.data_ptr(), stream_handle())
+    check(rc, "ntm_mx_compare")
+    raw = res.cpu().numpy().tobytes()
+    count = int.from_bytes(raw[0:8], "little")
+    if count == 0:
+        return MxCompareReport(0, None, None, None)
+    return MxCompareReport(count, int.from_bytes(raw[8:16], "little"),
+                           int.from_bytes(raw[16:20], "little"), int.from_bytes(raw[20:24], "little"))
 
 
 # K5: per-CU compute sweep (validation/include/ntm/cu_sweep.hpp, cu_sweep_plan.hpp).

@@ -296,3 +296,35 @@ def cu_sweep_expected(iters: int, seed: int, lds_bytes: int) -> dict:
     res["table"] = np.concatenate(rows)
     res["peak"] = peak
     return res
+
+
+# K7 on the CPU: the MX check's products come from the exact integer reference in ops/mx.py
+# (table decode, integer dot); tensors are CPU uint8 / fp32, nothing runs on a matrix core.
+from . import mx as _mx  # noqa: E402
+from .kernels import MxCompareReport, mx_check_args  # noqa: E402
+from .mx import (mx_dense_exact, mx_make_inputs, mx_matmul_bits, mx_pack,  # noqa: E402,F401
+                 mx_unpack)
+
+
+def mx_gemm(a, b, sa, sb, fmt, out: torch.Tensor | None = None) -> torch.Tensor:
+    mx_check_args(a, b, sa, sb, fmt, out, need_cuda=False)
+    bits = _mx.mx_matmul_bits(a.numpy(), b.numpy(), sa.numpy(), sb.numpy(), fmt)
+    c = torch.from_numpy(bits.view(np.float32).copy())
+    if out is None:
+        return c
+    out.copy_(c)
+    return out
+
+
+mx_reference_gpu = mx_gemm
+
+
+def mx_compare(expected: torch.Tensor, got: torch.Tensor) -> MxCompareReport:
+    e = _bytes_of(expected).view(np.uint32)
+    g = _bytes_of(got).view(np.uint32)
+    if e.size != g.size:
+        raise ValueError("mx_compare needs two tensors of one size")
+    idx = np.flatnonzero(e != g)
+    if not idx.size:
+        return MxCompareReport(0, None, None, None)
+    return MxCompareReport(int(idx.size), int(idx[0]), int(e[idx[0]]), int(g[idx[0]]))

@@ -33,6 +33,7 @@
 #include "ntm/gemm_w4k.hpp"
 #include "ntm/gemm_bf16_t128.hpp"
 #include "ntm/gemm_fp8_diag.hpp"
+#include "ntm/mx_gemm.hpp"
 #include "ntm/stream_policy_exp.hpp"
 
 #define NTM_API extern "C" __attribute__((visibility("default")))
@@ -252,6 +253,41 @@ NTM_API int ntm_mfma_f8_probe(const void* a_stage, const void* b_stage, float* d
   hipLaunchKernelGGL(ntm::fp8::mfma_f8_probe_kernel, dim3(1), dim3(64), 0, S(stream),
                      (const ntm::fp8::i32x8*)a_stage, (const ntm::fp8::i32x8*)b_stage,
                      (ntm::f32x4*)d);
+  return (int)hipGetLastError();
+}
+
+// K7 lane-map probe: one v_mfma_scale_f32_16x16x128_f8f6f4 in format fmt (both
+// operands) on caller-built register images: a_stage / b_stage 64 lanes x 32 B
+// (the 6- and 4-bit formats use the first 24 / 16 B of a lane), sa / sb 64
+// scale VGPRs (op_sel 0: the low byte counts), d 64 x 4 fp32 in the C/D layout.
+// A wrong operand or scale map shows in one run's output.
+namespace {
+template <int FMT>
+__global__ void __launch_bounds__(64) mx_mfma_probe_kernel(const ntm::mx::i32x8* a,
+                                                           const ntm::mx::i32x8* b, const int* sa,
+                                                           const int* sb, ntm::f32x4* d) {
+  const int l = threadIdx.x;
+  d[l] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[l], b[l], ntm::f32x4{0.f, 0.f, 0.f, 0.f},
+                                                          FMT, FMT, 0, sa[l], 0, sb[l]);
+}
+}  // namespace
+
+NTM_API int ntm_mx_mfma_probe(int fmt, const void* a_stage, const void* b_stage, const void* sa,
+                              const void* sb, float* d, void* stream) {
+  auto* a = (const ntm::mx::i32x8*)a_stage;
+  auto* b = (const ntm::mx::i32x8*)b_stage;
+  auto* x = (const int*)sa;
+  auto* y = (const int*)sb;
+  auto* o = (ntm::f32x4*)d;
+  if (!a || !b || !x || !y || !o) return (int)hipErrorInvalidValue;
+  switch (fmt) {
+    case 0: hipLaunchKernelGGL(mx_mfma_probe_kernel<0>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
+    case 1: hipLaunchKernelGGL(mx_mfma_probe_kernel<1>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
+    case 2: hipLaunchKernelGGL(mx_mfma_probe_kernel<2>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
+    case 3: hipLaunchKernelGGL(mx_mfma_probe_kernel<3>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
+    case 4: hipLaunchKernelGGL(mx_mfma_probe_kernel<4>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
+    default: return (int)hipErrorInvalidValue;
+  }
   return (int)hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // C ABI over the MI355X validation kernels (K1 GEMM, K2 HBM stream,
 // K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep,
-// K6 host-link check).
+// K6 host-link check, K7 MX block-scaled matrix check).
 // Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
@@ -25,6 +25,7 @@
 #include "ntm/gemm_w4k.hpp"
 #include "ntm/hbm_pattern.hpp"
 #include "ntm/host_link.hpp"
+#include "ntm/mx_gemm.hpp"
 
 #define NTM_API extern "C" __attribute__((visibility("default")))
 
@@ -990,3 +991,28 @@ NTM_API int ntm_host_link_clock_khz(int device) {
   }
   return v;
 }
+
+// K7: MX block-scaled matrix check (mx_gemm.hpp; host side in mx_plan.hpp).
+// fmt: 0 e4m3, 1 e5m2, 2 e2m3, 3 e3m2, 4 e2m1 for both operands; A / B row-major
+// packed (K * bits / 8 bytes per row, 16-byte aligned), SA[M][K/32] / SB[N][K/32]
+// E8M0 bytes, C fp32 [M][N]. M, N and K must be multiples of 128: anything
+// else returns hipErrorInvalidValue and launches nothing.
+NTM_API int ntm_mx_shape_ok(int M, int N, int K) { return ntm::mx::shape_ok(M, N, K) ? 1 : 0; }
+
+NTM_API int ntm_mx_gemm(int fmt, const void* A, const void* B, const void* SA, const void* SB,
+                        void* C, int M, int N, int K, void* stream) {
+  return (int)ntm::mx::launch_mx_gemm(fmt, A, B, SA, SB, (float*)C, M, N, K, S(stream));
+}
+
+// The same product without the matrix cores (mx_ref_kernel).
+NTM_API int ntm_mx_reference(int fmt, const void* A, const void* B, const void* SA, const void* SB,
+                             void* C, int M, int N, int K, void* stream) {
+  return (int)ntm::mx::launch_mx_reference(fmt, A, B, SA, SB, (float*)C, M, N, K, S(stream));
+}
+
+// Bitwise compare of n 32-bit words; `out`: one initialised ntm::mx::Mismatch
+// (24 bytes: count, first index = all ones, expected, got) in device memory.
+NTM_API int ntm_mx_compare(const void* expected, const void* got, size_t n, void* out, void* stream) {
+  return (int)ntm::mx::launch_mx_compare(expected, got, n, out, S(stream));
+}
+NTM_API int ntm_mx_mismatch_bytes() { return (int)sizeof(ntm::mx::Mismatch); }

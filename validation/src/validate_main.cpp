@@ -14,6 +14,9 @@
 //   K6  host-link (PCIe) check: verified transfers both ways through pinned
 //       host memory, rate and read latency, off by default
 //       (--host-link-mib; ntm/host_link.hpp)
+//   K7  MX block-scaled matrix check: MXFP8 / MXFP6 / MXFP4 GEMMs with real
+//       E8M0 scales, every element compared bitwise, off by default
+//       (--mx-check; ntm/mx_gemm.hpp)
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL
@@ -48,6 +51,7 @@
 #include "ntm/cu_sweep_plan.hpp"
 #include "ntm/hbm_test_plan.hpp"
 #include "ntm/host_link_plan.hpp"
+#include "ntm/mx_plan.hpp"
 
 namespace ntm {
 namespace xgmi {
@@ -97,6 +101,10 @@ int ntm_host_link_pull(const void*, size_t, unsigned long long, int, unsigned lo
                        int, void*, void*);
 int ntm_host_link_chase(const void*, unsigned long long, unsigned long long, unsigned, void*, void*);
 int ntm_host_link_clock_khz(int);
+int ntm_mx_gemm(int, const void*, const void*, const void*, const void*, void*, int, int, int, void*);
+int ntm_mx_reference(int, const void*, const void*, const void*, const void*, void*, int, int, int,
+                     void*);
+int ntm_mx_compare(const void*, const void*, size_t, void*, void*);
 }
 
 namespace {
@@ -137,6 +145,9 @@ struct Opts {
   int cu_sweep_iters = 16;      // rounds per workgroup (profiles/cu_sweep/README.md)
   long host_link_mib = 0;       // K6: 0 = off; MiB of pinned host memory per GPU
   double host_link_floor_gbps = 0;  // per direction, 0 = report only
+  bool mx_check = false;        // K7: off unless asked for
+  int mx_size = 4096;           // M = N = K of the dense e2m1 run (a multiple of 128)
+  double mx_tflops_floor = 0;   // 0 = report only
   long allreduce_max_mib = 8192;  // 8 GiB, capped by free HBM
   bool xgmi = true;
   int xgmi_sim = 0;             // C2 with N simulated ranks on GPU 0 (one-GPU test path)
@@ -171,6 +182,7 @@ void usage() {
                "       [--hbm-test-gb GB] [--hbm-test-passes P]\n"
                "       [--cu-sweep] [--cu-sweep-iters N]\n"
                "       [--host-link-mib MiB] [--host-link-floor-gbps GBps]\n"
+               "       [--mx-check] [--mx-size S] [--mx-tflops-floor TF]\n"
                "       [--allreduce-max-mib MiB] [--rccl | --no-rccl] [--no-xgmi] [--xgmi-sim N]\n"
                "       [--settle-s S] [--no-fp8] [--fp8-tflops-floor TF]\n"
                "       [--no-p2p] [--p2p-mib MiB] [--p2p-floor-gbps GBps] [--p2p-loopback]\n"
@@ -182,7 +194,7 @@ void usage() {
                "       [--pushgateway http://host:port]\n"
                "fault-inject (also env NTM_FAULT_INJECT): corrupt_gemm | corrupt_abft |\n"
                "       corrupt_fp8 | corrupt_fp8_abft | corrupt_p2p | corrupt_allreduce |\n"
-               "       corrupt_hbm | bad_cu | corrupt_host_link | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
+               "       corrupt_hbm | bad_cu | corrupt_host_link | corrupt_mx | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
                "       launch claims a wrong XCD; corrupt_hbm: one bit of the pattern test's\n"
                "       last chunk, needs --hbm-test-gb) to prove detection\n"
                "hbm-test-gb: K4, write / read back / compare an address pattern and a hash\n"
@@ -198,7 +210,15 @@ void usage() {
                "       both at once, hipMemcpyAsync both ways and the read latency; 0 = off\n"
                "       (default). host-link-floor-gbps: fail when a direction's faster path (kernel or\n"
                "       hipMemcpyAsync) is below GBps (0 = report only). fault-inject corrupt_host_link\n"
-               "       (needs --host-link-mib): the host flips one bit of the LAST GPU's pinned buffer\n");
+               "       (needs --host-link-mib): the host flips one bit of the LAST GPU's pinned buffer\n"
+               "mx-check: K7, block-scaled GEMMs on the scaled f8f6f4 matrix instruction with real\n"
+               "       E8M0 scales: a decode sweep of e4m3 / e5m2 / e2m3 / e3m2 / e2m1 against the\n"
+               "       host's integer table, dense e2m3 (K = 512) and dense e2m1 (mx-size^3,\n"
+               "       default 4096, a multiple of 128) against a reference kernel without matrix\n"
+               "       cores, every element compared bitwise, then a timed e2m1 loop;\n"
+               "       mx-tflops-floor: fail when that loop is below TF (0 = report only).\n"
+               "       fault-inject corrupt_mx (needs --mx-check): one bit of one element of the LAST\n"
+               "       GPU's dense e2m1 result is flipped before the compare\n");
 }
 
 bool parse(int argc, char** argv, Opts& o) {
@@ -222,6 +242,9 @@ bool parse(int argc, char** argv, Opts& o) {
     else if (a == "--cu-sweep") o.cu_sweep = true;
     else if (a == "--cu-sweep-iters") { if (!(v = next(a.c_str()))) return false; o.cu_sweep_iters = std::atoi(v); }
     else if (a == "--host-link-mib") { if (!(v = next(a.c_str()))) return false; o.host_link_mib = std::atol(v); }
+    else if (a == "--mx-check") o.mx_check = true;
+    else if (a == "--mx-size") { if (!(v = next(a.c_str()))) return false; o.mx_size = std::atoi(v); }
+    else if (a == "--mx-tflops-floor") { if (!(v = next(a.c_str()))) return false; o.mx_tflops_floor = std::atof(v); }
     else if (a == "--host-link-floor-gbps") { if (!(v = next(a.c_str()))) return false; o.host_link_floor_gbps = std::atof(v); }
     else if (a == "--hbm-test-passes") { if (!(v = next(a.c_str()))) return false; o.hbm_test_passes = std::atoi(v); }
     else if (a == "--allreduce-max-mib") { if (!(v = next(a.c_str()))) return false; o.allreduce_max_mib = std::atol(v); }
@@ -257,7 +280,9 @@ bool parse(int argc, char** argv, Opts& o) {
          o.xgmi_sim >= 0 && o.xgmi_sim <= ntm::xgmi::kMaxRanks && o.settle_s >= 0 &&
          o.hbm_test_passes >= 1 && std::isfinite(o.hbm_test_gb) && o.cu_sweep_iters >= 1 &&
          o.cu_sweep_iters <= ntm::cus::kMaxIters && o.host_link_mib >= 0 &&
-         o.host_link_mib <= (1l << 20) && o.host_link_floor_gbps >= 0;
+         o.host_link_mib <= (1l << 20) && o.host_link_floor_gbps >= 0 &&
+         ntm::mx::shape_ok(o.mx_size, o.mx_size, o.mx_size) && o.mx_size <= 16384 &&
+         o.mx_tflops_floor >= 0;
 }
 
 // ------------------------------------------------------------ JSON helpers
@@ -373,6 +398,13 @@ struct GpuResult {
   ntm::hostlink::LinkState host_link_pcie;
   double host_link_s = 0, host_link_pin_s = 0, host_link_xfer_s = 0, host_link_free_s = 0;
   std::vector<std::string> host_link_failures;  // empty = clean
+  // K7 (only with --mx-check)
+  bool mx_ran = false;
+  std::vector<std::string> mx_formats;  // formats whose every step compared clean
+  unsigned long long mx_bad_elements = 0;
+  double mx_fp4_tflops = 0, mx_s = 0;
+  int mx_scale_spread = 0;
+  std::vector<std::string> mx_failures;  // empty = clean
 };
 
 // The split-mode self-check shape: 48 x 5 of 192x256 tiles, half a round on
@@ -755,6 +787,138 @@ bool run_host_link(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& 
   return true;
 }
 
+// ---- K7: MX block-scaled matrix check (ntm/mx_gemm.hpp, host side in ntm/mx_plan.hpp).
+// Every answer is exact and every compare bitwise:
+//   1. the decode sweep of all five formats, 256 x 128 x 128, one non-zero per row of A,
+//      all 15 windows of A scale bytes 0 .. 254, against the host's integer table;
+//   2. dense e2m3, mx-size x mx-size x 512, and
+//   3. dense e2m1, mx-size^3, both with non-unit scales of the largest spread W <= 3
+//      the bound allows, against mx_ref_kernel (no matrix core);
+//   4. the e2m1 product timed: the settle of the other GEMM stages, then o.iters launches.
+// corrupt_mx: one bit of one element of the dense e2m1 result is flipped before the compare.
+bool run_mx_check(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r) {
+  namespace mx = ntm::mx;
+  const auto t_begin = Clock::now();
+  r.mx_ran = true;
+  const int S = o.mx_size;
+  mx::Mismatch init, got;
+  mx::mismatch_init(init);
+  mx::Mismatch* dres = nullptr;
+  CK(hipMalloc(&dres, sizeof init));
+  bool fmt_clean[mx::kFormats] = {true, true, true, true, true};
+  unsigned char *dA = nullptr, *dB = nullptr, *dSA = nullptr, *dSB = nullptr;
+  float *dC = nullptr, *dE = nullptr;
+  // One product: upload, run the GEMM, get the expected bits (host table or reference
+  // kernel), compare on the device. The buffers stay allocated for the timed loop.
+  auto product = [&](const mx::Inputs& in, const char* mode, bool host_table, bool inject) -> bool {
+    const size_t nc = (size_t)in.M * in.N;
+    CK(hipMalloc(&dA, in.a.size()));
+    CK(hipMalloc(&dB, in.b.size()));
+    CK(hipMalloc(&dSA, in.sa.size()));
+    CK(hipMalloc(&dSB, in.sb.size()));
+    CK(hipMalloc(&dC, nc * 4));
+    CK(hipMalloc(&dE, nc * 4));
+    CK(hipMemcpyAsync(dA, in.a.data(), in.a.size(), hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(dB, in.b.data(), in.b.size(), hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(dSA, in.sa.data(), in.sa.size(), hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(dSB, in.sb.data(), in.sb.size(), hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(dres, &init, sizeof init, hipMemcpyHostToDevice, s));
+    CK(hipMemsetAsync(dC, 0xFF, nc * 4, s));
+    CK(ntm_mx_gemm(in.fmt, dA, dB, dSA, dSB, dC, in.M, in.N, in.K, s));
+    std::vector<uint32_t> bits;
+    if (host_table) {
+      if (!mx::host_reference(in, bits)) {
+        fail("mx host reference: scale spread too wide");
+        return false;
+      }
+      CK(hipMemcpyAsync(dE, bits.data(), nc * 4, hipMemcpyHostToDevice, s));
+    } else {
+      CK(ntm_mx_reference(in.fmt, dA, dB, dSA, dSB, dE, in.M, in.N, in.K, s));
+    }
+    if (inject) {
+      uint32_t w;
+      float* at = dC + (nc / 2 + 5);
+      CK(hipMemcpyAsync(&w, at, 4, hipMemcpyDeviceToHost, s));
+      CK(hipStreamSynchronize(s));
+      w ^= 1u << 3;
+      CK(hipMemcpyAsync(at, &w, 4, hipMemcpyHostToDevice, s));
+    }
+    CK(ntm_mx_compare(dE, dC, nc, dres, s));
+    CK(hipMemcpyAsync(&got, dres, sizeof got, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
+    if (got.count) {
+      r.mx_bad_elements += got.count;
+      fmt_clean[in.fmt] = false;
+      // one line per format and mode: the first failing product names the element
+      const std::string head = "gpu" + std::to_string(dev) + ": mx " + mx::format_name(in.fmt) + " " + mode + ":";
+      bool seen = false;
+      for (auto& f : r.mx_failures) seen = seen || f.compare(0, head.size(), head) == 0;
+      if (!seen) r.mx_failures.push_back(mx::failure_message(dev, in.fmt, mode, got, in.N));
+    }
+    return true;
+  };
+  auto release = [&]() -> bool {
+    CK(hipFree(dA));
+    CK(hipFree(dB));
+    CK(hipFree(dSA));
+    CK(hipFree(dSB));
+    CK(hipFree(dC));
+    CK(hipFree(dE));
+    dA = dB = dSA = dSB = nullptr;
+    dC = dE = nullptr;
+    return true;
+  };
+  for (int fmt = 0; fmt < mx::kFormats; ++fmt)
+    for (int w = 0; w < mx::kDecodeWindows; ++w) {
+      if (!product(mx::make_decode(fmt, 256, 128, 128, w), "decode", true, false)) return false;
+      if (!release()) return false;
+    }
+  const unsigned long long seed = 0x4B37ull + (unsigned)dev;
+  const int w6 = mx::dense_max_spread(mx::kFmtE2M3, 512);
+  if (w6 >= 0) {
+    if (!product(mx::make_dense(mx::kFmtE2M3, S, S, 512, seed, w6), "dense", false, false)) return false;
+    if (!release()) return false;
+  }
+  const int w4 = mx::dense_max_spread(mx::kFmtE2M1, S);
+  if (w4 < 0) {
+    r.mx_failures.push_back("gpu" + std::to_string(dev) + ": mx e2m1 dense: no exact scale spread at size " +
+                            std::to_string(S));
+    fmt_clean[mx::kFmtE2M1] = false;
+  } else {
+    r.mx_scale_spread = w4;
+    if (!product(mx::make_dense(mx::kFmtE2M1, S, S, S, seed, w4), "dense", false,
+                 last && o.fault == "corrupt_mx"))
+      return false;
+    // timed: the buffers of the dense e2m1 product are still in place
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    const auto t0 = Clock::now();
+    do {
+      for (int i = 0; i < 8; ++i) CK(ntm_mx_gemm(mx::kFmtE2M1, dA, dB, dSA, dSB, dC, S, S, S, s));
+      CK(hipStreamSynchronize(s));
+    } while (std::chrono::duration<double>(Clock::now() - t0).count() < o.settle_s);
+    CK(hipEventRecord(e0, s));
+    for (int i = 0; i < o.iters; ++i) CK(ntm_mx_gemm(mx::kFmtE2M1, dA, dB, dSA, dSB, dC, S, S, S, s));
+    CK(hipEventRecord(e1, s));
+    CK(hipEventSynchronize(e1));
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    r.mx_fp4_tflops = 2.0 * S * (double)S * S / (ms / o.iters * 1e-3) / 1e12;
+    CK(hipEventDestroy(e0));
+    CK(hipEventDestroy(e1));
+    if (!release()) return false;
+    if (o.mx_tflops_floor > 0 && r.mx_fp4_tflops < o.mx_tflops_floor)
+      r.mx_failures.push_back("gpu" + std::to_string(dev) + ": mx e2m1 GEMM " + jnum(r.mx_fp4_tflops) +
+                              " TFLOP/s below floor " + jnum(o.mx_tflops_floor));
+  }
+  CK(hipFree(dres));
+  for (int fmt = 0; fmt < mx::kFormats; ++fmt)
+    if (fmt_clean[fmt]) r.mx_formats.push_back(mx::format_name(fmt));
+  r.mx_s = std::chrono::duration<double>(Clock::now() - t_begin).count();
+  return true;
+}
+
 bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   r.device = dev;
   CK(hipSetDevice(dev));
@@ -993,6 +1157,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   if (o.hbm_test_gb != 0 && !run_hbm_test(dev, last, o, s, r)) return false;
   if (o.cu_sweep && !run_cu_sweep(dev, last, o, s, r)) return false;
   if (o.host_link_mib > 0 && !run_host_link(dev, last, o, s, r)) return false;
+  if (o.mx_check && !run_mx_check(dev, last, o, s, r)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));
@@ -1687,6 +1852,7 @@ int main(int argc, char** argv) {
     if (!r.hbm_test_failure.empty()) fail(r.hbm_test_failure);
     if (!r.cu_sweep_failure.empty()) fail(r.cu_sweep_failure);
     for (auto& f : r.host_link_failures) fail(f);
+    for (auto& f : r.mx_failures) fail(f);
     if (o.hbm_floor_gbps > 0 && r.hbm_copy_gbps < o.hbm_floor_gbps)
       fail(d + "HBM copy " + jnum(r.hbm_copy_gbps) + " GB/s below floor");
   }
@@ -1784,6 +1950,24 @@ int main(int argc, char** argv) {
       gauge("bad_words", "8-byte words that crossed the host link wrong.",
             [](const GpuResult& r) { return std::to_string(r.host_link_bad_words); });
     }
+    if (o.mx_check) {
+      auto gauge = [&](const char* name, const char* help, auto value) {
+        p << "# HELP amdgpu_validate_mx_" << name << " " << help << "\n"
+          << "# TYPE amdgpu_validate_mx_" << name << " gauge\n";
+        for (auto& r : res)
+          if (r.mx_ran)
+            p << "amdgpu_validate_mx_" << name << "{gpu=\"" << r.device << "\"} " << value(r) << "\n";
+      };
+      gauge("formats", "MX element formats whose every step compared clean (of 5).",
+            [](const GpuResult& r) { return std::to_string(r.mx_formats.size()); });
+      gauge("bad_elements", "Elements of the MX block-scaled GEMMs that differ bitwise from the exact answer.",
+            [](const GpuResult& r) { return std::to_string(r.mx_bad_elements); });
+      gauge("fp4_tflops", "TFLOP/s of the dense MXFP4 (e2m1) GEMM.",
+            [](const GpuResult& r) { return jnum(r.mx_fp4_tflops); });
+      gauge("scale_spread", "Scale spread W (k-block scale exponents base .. base + W) of the dense e2m1 run.",
+            [](const GpuResult& r) { return std::to_string(r.mx_scale_spread); });
+      gauge("s", "Seconds the MX check took.", [](const GpuResult& r) { return jnum(r.mx_s); });
+    }
     if (!rccl_rows.empty() || !xgmi_rows.empty())
       p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
         << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(peak_rccl) << "\n"
@@ -1867,6 +2051,14 @@ int main(int argc, char** argv) {
             ",\"host_link_pin_s\":" + jnum(r.host_link_pin_s) +
             ",\"host_link_transfer_s\":" + jnum(r.host_link_xfer_s) +
             ",\"host_link_free_s\":" + jnum(r.host_link_free_s);
+    if (r.mx_ran) {
+      js += ",\"mx_formats\":[";
+      for (size_t i = 0; i < r.mx_formats.size(); ++i) js += (i ? "," : "") + jstr(r.mx_formats[i]);
+      js += "],\"mx_bad_elements\":" + std::to_string(r.mx_bad_elements) +
+            ",\"mx_fp4_tflops\":" + jnum(r.mx_fp4_tflops) +
+            ",\"mx_scale_spread\":" + std::to_string(r.mx_scale_spread) +
+            ",\"mx_s\":" + jnum(r.mx_s);
+    }
     js += "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(rccl_rows);
