@@ -60,6 +60,9 @@ locals {
     ] : [],
     # K7: the MX block-scaled matrix check (MXFP8 / MXFP6 / MXFP4), off unless asked for
     var.validation_mx_check ? ["--mx-check"] : [],
+    # K8: the per-XCD sweep, off unless asked for; the ratio only when it gates
+    var.validation_xcd_sweep ? ["--xcd-sweep"] : [],
+    var.validation_xcd_sweep && var.validation_xcd_ratio > 0 ? ["--xcd-ratio", tostring(var.validation_xcd_ratio)] : [],
     # one-line verdict surfaced as the pod's termination message
     ["--termination-log", "/dev/termination-log"],
   )

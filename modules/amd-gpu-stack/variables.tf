@@ -346,6 +346,23 @@ variable "validation_mx_check" {
   description = "Run the Job's MX block-scaled matrix check (K7): GEMMs on the scaled f8f6f4 matrix instruction with real E8M0 scales per 32-element block - a decode sweep of e4m3, e5m2, e2m3, e3m2 and e2m1 against an integer table, dense MXFP6 (e2m3) and dense MXFP4 (e2m1, 4096^3) against a reference kernel that uses no matrix core - every element compared bitwise, then the MXFP4 rate (reported only). A wrong element fails the Job; the message names the GPU, the format, row, column, expected and got. Measurements: profiles/mx/README.md."
 }
 
+variable "validation_xcd_sweep" {
+  type        = bool
+  default     = false
+  description = "Run the Job's per-XCD sweep (K8): every XCD reads and verifies its own slice of a hash-pattern buffer through a work queue of its own, alone and all together, at 1 MiB, 16 MiB and 256 MiB per XCD, plus a bf16 MFMA clock probe; each XCD is timed against its own stamps. Wrong data, a lost tile or an XCD short of a CU fails the Job by XCD; rates and clocks per XCD are reported. The default false leaves the Job unchanged. Measurements: profiles/xcd_sweep/README.md."
+}
+
+variable "validation_xcd_ratio" {
+  type        = number
+  default     = 0
+  description = "With validation_xcd_sweep: fail an XCD whose rate at a level and mode is below this fraction of the median of its own card's XCDs; 0 (the default) reports only. Measured on healthy MI355X hardware in two sessions of five runs (profiles/xcd_sweep/README.md): over the judged cells the lowest min / median was 0.953 and the largest run-to-run range of that number 0.031, so 0.90 (0.953 - 0.031, rounded down) is the recommended gate. mall / together and hbm / together moved by more than 0.1 between sessions (0.84 - 0.97 and 0.76 - 0.92) and are reported, not judged. A genuinely degraded XCD has not been measured."
+
+  validation {
+    condition     = var.validation_xcd_ratio >= 0 && var.validation_xcd_ratio < 1
+    error_message = "validation_xcd_ratio must be >= 0 and < 1."
+  }
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

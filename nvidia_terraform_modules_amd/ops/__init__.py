@@ -18,6 +18,8 @@ K7 ``mx_gemm``, ``mx_reference_gpu``, ``mx_compare`` - a block-scaled GEMM in th
    (e4m3, e5m2, e2m3, e3m2, e2m1 with E8M0 scales) on the scaled f8f6f4 matrix instruction, a
    reference without matrix cores and a bitwise compare; ``mx_pack``, ``mx_unpack``,
    ``mx_make_inputs``, ``mx_dense_exact`` - the host side (numpy, ``ops.mx``).
+K8 ``xcd_sweep_read``, ``xcd_sweep_mfma``, ``xcd_sweep_summarize`` - a verified read and an
+   MFMA clock probe per XCD, each XCD timed against its own stamps.
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -82,6 +84,14 @@ from .kernels import (  # noqa: F401
     cu_sweep_max_lds_bytes,
     cu_sweep_record_dtype,
     cu_sweep_summarize,
+    XCD_SWEEP_LEVELS,
+    XCD_SWEEP_MODES,
+    xcd_sweep_gated,
+    xcd_sweep_mfma,
+    xcd_sweep_read,
+    xcd_sweep_record_dtype,
+    xcd_sweep_summarize,
+    xcd_sweep_xcds,
     verify_bf16,
 )
 from .mx import (  # noqa: F401

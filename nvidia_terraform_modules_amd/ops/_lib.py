@@ -129,6 +129,18 @@ def _declare(lib: ctypes.CDLL) -> None:
         "ntm_cu_sweep_decode": ([ctypes.c_uint, ctypes.c_uint, c_vp], None),
         "ntm_cu_sweep_summarize": ([c_vp, c_size, ctypes.c_uint, ctypes.c_uint, c_int, c_vp, c_size],
                                    c_size),
+        "ntm_xcd_sweep_record_bytes": ([], c_int),
+        "ntm_xcd_sweep_heads_bytes": ([], c_int),
+        "ntm_xcd_sweep_tile_bytes": ([], c_int),
+        "ntm_xcd_sweep_mfma_per_batch": ([], c_int),
+        "ntm_xcd_sweep_gated": ([c_int, c_int], c_int),
+        "ntm_xcd_sweep_read_launch": ([c_vp, c_size, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_int,
+                                       ctypes.c_ulonglong, ctypes.c_uint, c_int, ctypes.c_uint, c_vp, c_vp,
+                                       c_vp], c_int),
+        "ntm_xcd_sweep_mfma_launch": ([ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
+                                       ctypes.c_uint, c_int, ctypes.c_uint, c_vp, c_vp, c_vp], c_int),
+        "ntm_xcd_sweep_summarize": ([c_vp, c_size, c_int, c_int, ctypes.c_uint, ctypes.c_uint,
+                                     ctypes.c_ulonglong, ctypes.c_double, c_int, c_vp, c_size], c_size),
     }
     for name, (argt, rest) in sig.items():
         fn = getattr(lib, name)

@@ -1,6 +1,6 @@
 // C ABI over the MI355X validation kernels (K1 GEMM, K2 HBM stream,
 // K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep,
-// K6 host-link check, K7 MX block-scaled matrix check).
+// K6 host-link check, K7 MX block-scaled matrix check, K8 per-XCD sweep).
 // Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
@@ -26,6 +26,7 @@
 #include "ntm/hbm_pattern.hpp"
 #include "ntm/host_link.hpp"
 #include "ntm/mx_gemm.hpp"
+#include "ntm/xcd_sweep.hpp"
 
 #define NTM_API extern "C" __attribute__((visibility("default")))
 
@@ -1016,3 +1017,48 @@ NTM_API int ntm_mx_compare(const void* expected, const void* got, size_t n, void
   return (int)ntm::mx::launch_mx_compare(expected, got, n, out, S(stream));
 }
 NTM_API int ntm_mx_mismatch_bytes() { return (int)sizeof(ntm::mx::Mismatch); }
+
+// K8: per-XCD sweep (xcd_sweep.hpp; record, aggregation and verdict in
+// xcd_sweep_plan.hpp). The read launch takes a buffer of xcds * slice_bytes that
+// ntm_hbm_pattern_write filled from logical byte 0, `heads` (device,
+// ntm_xcd_sweep_heads_bytes(), zeroed here) and `records` (device, grid * 64
+// bytes, every one written). slow_xcd = -1: no injection.
+NTM_API int ntm_xcd_sweep_record_bytes() { return (int)sizeof(ntm::xcs::Record); }
+NTM_API int ntm_xcd_sweep_heads_bytes() { return (int)ntm::xcs::kHeadsBytes; }
+NTM_API int ntm_xcd_sweep_tile_bytes() { return (int)ntm::xcs::kTileBytes; }
+NTM_API int ntm_xcd_sweep_mfma_per_batch() { return (int)ntm::xcs::kMfmaPerBatch; }
+// 1 when the rate rule judges the cell, 0 when it is reported only
+NTM_API int ntm_xcd_sweep_gated(int level, int mode) { return ntm::xcs::gated(level, mode) ? 1 : 0; }
+
+NTM_API int ntm_xcd_sweep_read_launch(const void* buf, size_t slice_bytes, unsigned xcds,
+                                      unsigned xcd_mask, unsigned passes, int pattern,
+                                      unsigned long long seed, unsigned grid, int slow_xcd,
+                                      unsigned slow_factor, void* heads, void* records, void* stream) {
+  return (int)ntm::xcs::launch_xcd_read(buf, slice_bytes, xcds, xcd_mask, passes, pattern, seed, grid,
+                                        slow_xcd, slow_factor, (uint32_t*)heads,
+                                        (ntm::xcs::Record*)records, S(stream));
+}
+
+NTM_API int ntm_xcd_sweep_mfma_launch(unsigned grid, unsigned batches, unsigned seed, unsigned xcds,
+                                      unsigned xcd_mask, int slow_xcd, unsigned slow_factor,
+                                      void* records, float* sink, void* stream) {
+  return (int)ntm::xcs::launch_xcd_mfma(grid, batches, seed, xcds, xcd_mask, slow_xcd, slow_factor,
+                                        (ntm::xcs::Record*)records, sink, S(stream));
+}
+
+// Host-only. Aggregates n host records (one launch, or launches with disjoint
+// masks concatenated) per XCD into a JSON object (xcd_sweep_plan.hpp
+// summary_json). level / mode: the plan's ids; expected_tiles: what every XCD in
+// `mask` must have pulled (0 = not checked). Returns the JSON's length; it is
+// written (NUL-terminated) only when it fits in `cap`.
+NTM_API size_t ntm_xcd_sweep_summarize(const void* records, size_t n, int level, int mode, unsigned xcds,
+                                       unsigned mask, unsigned long long expected_tiles, double ratio,
+                                       int gpu, char* json, size_t cap) {
+  if (level < 0 || level >= ntm::xcs::kLevels || mode < 0 || mode >= ntm::xcs::kModes) return 0;
+  std::vector<ntm::xcs::Record> recs(n);
+  if (n) std::memcpy(recs.data(), records, n * sizeof(ntm::xcs::Record));
+  const std::string j = ntm::xcs::summary_json(
+      ntm::xcs::summarize(recs.data(), n, level, mode, xcds, mask, expected_tiles, ratio, gpu));
+  if (json && j.size() < cap) std::memcpy(json, j.c_str(), j.size() + 1);
+  return j.size();
+}

@@ -17,6 +17,8 @@
 //   K7  MX block-scaled matrix check: MXFP8 / MXFP6 / MXFP4 GEMMs with real
 //       E8M0 scales, every element compared bitwise, off by default
 //       (--mx-check; ntm/mx_gemm.hpp)
+//   K8  per-XCD sweep that names a slow or wrong XCD, off by default
+//       (--xcd-sweep; ntm/xcd_sweep.hpp)
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL
@@ -52,6 +54,7 @@
 #include "ntm/hbm_test_plan.hpp"
 #include "ntm/host_link_plan.hpp"
 #include "ntm/mx_plan.hpp"
+#include "ntm/xcd_sweep_plan.hpp"
 
 namespace ntm {
 namespace xgmi {
@@ -105,6 +108,10 @@ int ntm_mx_gemm(int, const void*, const void*, const void*, const void*, void*, 
 int ntm_mx_reference(int, const void*, const void*, const void*, const void*, void*, int, int, int,
                      void*);
 int ntm_mx_compare(const void*, const void*, size_t, void*, void*);
+int ntm_xcd_sweep_read_launch(const void*, size_t, unsigned, unsigned, unsigned, int, unsigned long long,
+                              unsigned, int, unsigned, void*, void*, void*);
+int ntm_xcd_sweep_mfma_launch(unsigned, unsigned, unsigned, unsigned, unsigned, int, unsigned, void*,
+                              float*, void*);
 }
 
 namespace {
@@ -148,6 +155,9 @@ struct Opts {
   bool mx_check = false;        // K7: off unless asked for
   int mx_size = 4096;           // M = N = K of the dense e2m1 run (a multiple of 128)
   double mx_tflops_floor = 0;   // 0 = report only
+  bool xcd_sweep = false;       // K8: off unless asked for
+  long xcd_sweep_mib = 256;     // MiB per XCD of the hbm level
+  double xcd_ratio = 0;         // fail an XCD below ratio x its card's median; 0 = report only
   long allreduce_max_mib = 8192;  // 8 GiB, capped by free HBM
   bool xgmi = true;
   int xgmi_sim = 0;             // C2 with N simulated ranks on GPU 0 (one-GPU test path)
@@ -183,6 +193,7 @@ void usage() {
                "       [--cu-sweep] [--cu-sweep-iters N]\n"
                "       [--host-link-mib MiB] [--host-link-floor-gbps GBps]\n"
                "       [--mx-check] [--mx-size S] [--mx-tflops-floor TF]\n"
+               "       [--xcd-sweep] [--xcd-sweep-mib MiB] [--xcd-ratio R]\n"
                "       [--allreduce-max-mib MiB] [--rccl | --no-rccl] [--no-xgmi] [--xgmi-sim N]\n"
                "       [--settle-s S] [--no-fp8] [--fp8-tflops-floor TF]\n"
                "       [--no-p2p] [--p2p-mib MiB] [--p2p-floor-gbps GBps] [--p2p-loopback]\n"
@@ -194,7 +205,7 @@ void usage() {
                "       [--pushgateway http://host:port]\n"
                "fault-inject (also env NTM_FAULT_INJECT): corrupt_gemm | corrupt_abft |\n"
                "       corrupt_fp8 | corrupt_fp8_abft | corrupt_p2p | corrupt_allreduce |\n"
-               "       corrupt_hbm | bad_cu | corrupt_host_link | corrupt_mx | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
+               "       corrupt_hbm | bad_cu | corrupt_host_link | corrupt_mx | slow_xcd | corrupt_xcd | sk_xcc - corrupts the LAST GPU's data (sk_xcc: its stream-K\n"
                "       launch claims a wrong XCD; corrupt_hbm: one bit of the pattern test's\n"
                "       last chunk, needs --hbm-test-gb) to prove detection\n"
                "hbm-test-gb: K4, write / read back / compare an address pattern and a hash\n"
@@ -218,7 +229,17 @@ void usage() {
                "       cores, every element compared bitwise, then a timed e2m1 loop;\n"
                "       mx-tflops-floor: fail when that loop is below TF (0 = report only).\n"
                "       fault-inject corrupt_mx (needs --mx-check): one bit of one element of the LAST\n"
-               "       GPU's dense e2m1 result is flipped before the compare\n");
+               "       GPU's dense e2m1 result is flipped before the compare\n"
+               "xcd-sweep: K8, every XCD reads its own slice of a hash-pattern buffer through a work\n"
+               "       queue of its own, compares every word and is timed against its own stamps:\n"
+               "       alone and all together, at 1 MiB (l2), 16 MiB (mall) and xcd-sweep-mib (hbm,\n"
+               "       default 256) per XCD, plus a bf16 MFMA clock probe. Wrong data, a lost tile or\n"
+               "       a missing CU fail; xcd-ratio R (0 <= R < 1, default 0 = report only) also fails\n"
+               "       an XCD whose rate is below R x the median of its card's XCDs (mall / together\n"
+               "       and hbm / together are reported, not judged). fault-inject\n"
+               "       slow_xcd / corrupt_xcd (need --xcd-sweep): XCD 5 of the LAST GPU (XCD 0 on a\n"
+               "       partitioned device) runs at a quarter of its rate / one bit of XCD 3's hbm\n"
+               "       slice is flipped after the fill\n");
 }
 
 bool parse(int argc, char** argv, Opts& o) {
@@ -245,6 +266,9 @@ bool parse(int argc, char** argv, Opts& o) {
     else if (a == "--mx-check") o.mx_check = true;
     else if (a == "--mx-size") { if (!(v = next(a.c_str()))) return false; o.mx_size = std::atoi(v); }
     else if (a == "--mx-tflops-floor") { if (!(v = next(a.c_str()))) return false; o.mx_tflops_floor = std::atof(v); }
+    else if (a == "--xcd-sweep") o.xcd_sweep = true;
+    else if (a == "--xcd-sweep-mib") { if (!(v = next(a.c_str()))) return false; o.xcd_sweep_mib = std::atol(v); }
+    else if (a == "--xcd-ratio") { if (!(v = next(a.c_str()))) return false; o.xcd_ratio = std::atof(v); }
     else if (a == "--host-link-floor-gbps") { if (!(v = next(a.c_str()))) return false; o.host_link_floor_gbps = std::atof(v); }
     else if (a == "--hbm-test-passes") { if (!(v = next(a.c_str()))) return false; o.hbm_test_passes = std::atoi(v); }
     else if (a == "--allreduce-max-mib") { if (!(v = next(a.c_str()))) return false; o.allreduce_max_mib = std::atol(v); }
@@ -282,7 +306,8 @@ bool parse(int argc, char** argv, Opts& o) {
          o.cu_sweep_iters <= ntm::cus::kMaxIters && o.host_link_mib >= 0 &&
          o.host_link_mib <= (1l << 20) && o.host_link_floor_gbps >= 0 &&
          ntm::mx::shape_ok(o.mx_size, o.mx_size, o.mx_size) && o.mx_size <= 16384 &&
-         o.mx_tflops_floor >= 0;
+         o.mx_tflops_floor >= 0 && o.xcd_sweep_mib >= 1 && o.xcd_sweep_mib <= 4096 &&
+         o.xcd_ratio >= 0 && o.xcd_ratio < 1;
 }
 
 // ------------------------------------------------------------ JSON helpers
@@ -352,6 +377,14 @@ __global__ void check_pattern(const T* x, size_t n, int nranks,
 }
 
 // -------------------------------------------------------------- per GPU
+// K8: one level and mode of the per-XCD sweep
+struct XcdCell {
+  ntm::xcs::Summary sum;
+  uint32_t passes = 0;       // read: passes over the slice; mfma: batches per wave
+  uint64_t min_span_ticks = 0, max_span_ticks = 0;  // over the XCDs that timed something
+  bool gated = false;        // the rate rule judges this cell (ntm::xcs::gated)
+};
+
 struct GpuResult {
   int device = -1;
   std::string name, arch;
@@ -405,6 +438,12 @@ struct GpuResult {
   double mx_fp4_tflops = 0, mx_s = 0;
   int mx_scale_spread = 0;
   std::vector<std::string> mx_failures;  // empty = clean
+  // K8 (only with --xcd-sweep)
+  bool xcd_ran = false;
+  uint32_t xcd_xcds = 0;
+  std::vector<XcdCell> xcd_cells;   // one per level and mode that ran
+  std::vector<std::string> xcd_failures;
+  double xcd_s = 0;
 };
 
 // The split-mode self-check shape: 48 x 5 of 192x256 tiles, half a round on
@@ -919,6 +958,118 @@ bool run_mx_check(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r
   return true;
 }
 
+// ---- K8: per-XCD sweep (ntm/xcd_sweep.hpp, host side in ntm/xcd_sweep_plan.hpp).
+// One buffer of xcds x xcd-sweep-mib, filled once with K4's hash pattern; the l2 and
+// mall levels read its first xcds x 1 MiB / 16 MiB (the pattern depends on the position
+// alone). Per level: mode alone (one launch per XCD) and together (one launch). Every
+// cell runs once untimed with a first guess of the passes, which warms it up and sizes
+// the passes for spans of at least 100 us, then once for the record. slow_xcd and
+// corrupt_xcd act on the LAST GPU.
+bool run_xcd_sweep(int dev, bool last, const Opts& o, hipStream_t s, GpuResult& r) {
+  namespace xs = ntm::xcs;
+  const auto t_begin = Clock::now();
+  hipDeviceProp_t prop;
+  CK(hipGetDeviceProperties(&prop, dev));
+  const uint32_t xcds = std::min<uint32_t>(xs::xcds_expected((uint32_t)prop.multiProcessorCount), xs::kMaxXcds);
+  const std::string head = "gpu" + std::to_string(dev) + ": XCD sweep: ";
+  r.xcd_ran = true;
+  r.xcd_xcds = xcds;
+  if (xcds < 1) {
+    r.xcd_failures.push_back(head + "the device reports " + std::to_string(prop.multiProcessorCount) +
+                             " CUs, fewer than one XCD");
+    return true;
+  }
+  const uint32_t hbm_mib = (uint32_t)o.xcd_sweep_mib;
+  const size_t bytes = (size_t)xcds * hbm_mib << 20;
+  const uint32_t grid = xs::grid_of(xcds, xs::kWgPerCu), mfma_grid = xs::grid_of(xcds, 1);
+  const uint32_t all = xs::full_mask(xcds);
+  const unsigned long long seed = 0x4B38ull + (unsigned)dev;
+  const int slow_xcd = last && o.fault == "slow_xcd" ? (xcds > 5 ? 5 : 0) : xs::kSlowOff;
+  const uint32_t slow_factor = slow_xcd == xs::kSlowOff ? 1 : 4;
+  void *buf = nullptr, *heads = nullptr, *drec = nullptr, *sink = nullptr;
+  CK(hipMalloc(&buf, bytes));
+  CK(hipMalloc(&heads, xs::kHeadsBytes));
+  CK(hipMalloc(&drec, (size_t)grid * sizeof(xs::Record)));
+  CK(hipMalloc(&sink, 256));
+  CK(ntm_hbm_pattern_write(buf, bytes, 0, ntm::hbm::kPatternHash, seed, 0, s));
+  CK(hipStreamSynchronize(s));
+
+  bool hip_ok = true;
+  std::vector<xs::Record> one;
+  // one launch; its records are appended to `recs`
+  auto launch = [&](int level, uint32_t mask, uint32_t passes, std::vector<xs::Record>& recs) {
+    const bool mfma = level == xs::kLevelMfma;
+    const uint32_t g = mfma ? mfma_grid : grid;
+    one.resize(g);
+    const int rc = mfma ? ntm_xcd_sweep_mfma_launch(g, passes, 7u, xcds, mask, slow_xcd, slow_factor, drec,
+                                                    (float*)sink, s)
+                        : ntm_xcd_sweep_read_launch(buf, (size_t)xs::level_mib(level, hbm_mib) << 20, xcds,
+                                                    mask, passes, ntm::hbm::kPatternHash, seed, g, slow_xcd,
+                                                    slow_factor, heads, drec, s);
+    hip_ok = hip_ok && rc == 0 &&
+             hipMemcpyAsync(one.data(), drec, one.size() * sizeof(xs::Record), hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipStreamSynchronize(s) == hipSuccess;
+    if (hip_ok) recs.insert(recs.end(), one.begin(), one.end());
+    return hip_ok;
+  };
+  auto run_cell = [&](int level, int mode, uint32_t passes, double ratio) {
+    std::vector<xs::Record> recs;
+    if (mode == xs::kModeAlone) {
+      for (uint32_t x = 0; x < xcds && hip_ok; ++x) launch(level, 1u << x, passes, recs);
+    } else {
+      launch(level, all, passes, recs);
+    }
+    const uint64_t expected =
+        level == xs::kLevelMfma ? 0 : xs::expected_tiles((uint64_t)xs::level_mib(level, hbm_mib) << 20, passes);
+    XcdCell c;
+    c.passes = passes;
+    c.sum = xs::summarize(recs.data(), recs.size(), level, mode, xcds, all, expected, ratio, dev);
+    c.min_span_ticks = xs::min_timed_span(c.sum);
+    for (auto& row : c.sum.rows) c.max_span_ticks = std::max(c.max_span_ticks, row.span_ticks);
+    return c;
+  };
+  for (int level = 0; level < xs::kLevels && hip_ok; ++level) {
+    if (level == xs::kLevelHbm && last && o.fault == "corrupt_xcd") {
+      // one bit of a word in the middle of XCD 3's hbm slice (the last XCD's on a smaller device)
+      const size_t off = ((size_t)std::min<uint32_t>(3, xcds - 1) * hbm_mib << 20) + ((size_t)hbm_mib << 19) + 40;
+      uint32_t w = 0;
+      CK(hipMemcpy(&w, (char*)buf + off, 4, hipMemcpyDeviceToHost));
+      w ^= 1u << 9;
+      CK(hipMemcpy((char*)buf + off, &w, 4, hipMemcpyHostToDevice));
+    }
+    for (int mode = 0; mode < xs::kModes && hip_ok; ++mode) {
+      if (level == xs::kLevelMfma && mode == xs::kModeAlone) continue;  // the clock probe loads every XCD at once
+      const uint32_t first = level == xs::kLevelL2 ? 64 : level == xs::kLevelMall ? 4 : level == xs::kLevelHbm ? 1 : 16;
+      XcdCell c = run_cell(level, mode, first, 0);
+      uint32_t passes = first;
+      for (int attempt = 0; attempt < 2 && hip_ok; ++attempt) {
+        // sized from the XCDs that pulled tiles; one that ran nothing fails on its own
+        passes = xs::passes_for_min_span(passes, c.min_span_ticks);
+        if (level == xs::kLevelMfma) passes = std::min(passes, xs::kMaxMfmaBatches);
+        while (level != xs::kLevelMfma && passes > 1 &&
+               !xs::passes_ok((uint64_t)xs::level_mib(level, hbm_mib) << 20, passes))
+          passes /= 2;
+        c = run_cell(level, mode, passes, xs::gated(level, mode) ? o.xcd_ratio : 0);
+        if (c.min_span_ticks == 0 || c.min_span_ticks >= xs::kMinSpanTicks) break;
+      }
+      c.gated = xs::gated(level, mode);
+      if (!hip_ok) break;
+      for (auto& f : c.sum.failures) r.xcd_failures.push_back(f);
+      r.xcd_cells.push_back(std::move(c));
+    }
+  }
+  if (!hip_ok) {
+    fail(head + "HIP error " + hipGetErrorString(hipGetLastError()));
+    return false;
+  }
+  CK(hipFree(buf));
+  CK(hipFree(heads));
+  CK(hipFree(drec));
+  CK(hipFree(sink));
+  r.xcd_s = std::chrono::duration<double>(Clock::now() - t_begin).count();
+  return true;
+}
+
 bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   r.device = dev;
   CK(hipSetDevice(dev));
@@ -1158,6 +1309,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   if (o.cu_sweep && !run_cu_sweep(dev, last, o, s, r)) return false;
   if (o.host_link_mib > 0 && !run_host_link(dev, last, o, s, r)) return false;
   if (o.mx_check && !run_mx_check(dev, last, o, s, r)) return false;
+  if (o.xcd_sweep && !run_xcd_sweep(dev, last, o, s, r)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));
@@ -1794,6 +1946,11 @@ int main(int argc, char** argv) {
   }
   if (o.fault.empty())
     if (const char* f = std::getenv("NTM_FAULT_INJECT")) o.fault = f;
+  if ((o.fault == "slow_xcd" || o.fault == "corrupt_xcd") && !o.xcd_sweep) {
+    std::fprintf(stderr, "fault-inject %s needs --xcd-sweep\n", o.fault.c_str());
+    usage();
+    return 2;
+  }
   const HostPrep hp = read_host_prep();
   if (o.require_host_prep || o.require_iommu_pt) {
     if (hp.numa_balancing != 0)
@@ -1853,6 +2010,7 @@ int main(int argc, char** argv) {
     if (!r.cu_sweep_failure.empty()) fail(r.cu_sweep_failure);
     for (auto& f : r.host_link_failures) fail(f);
     for (auto& f : r.mx_failures) fail(f);
+    for (auto& f : r.xcd_failures) fail(f);
     if (o.hbm_floor_gbps > 0 && r.hbm_copy_gbps < o.hbm_floor_gbps)
       fail(d + "HBM copy " + jnum(r.hbm_copy_gbps) + " GB/s below floor");
   }
@@ -1949,6 +2107,21 @@ int main(int argc, char** argv) {
             [](const GpuResult& r) { return jnum(std::max(r.host_link_d2h_gbps, r.host_link_d2h_copy_gbps)); });
       gauge("bad_words", "8-byte words that crossed the host link wrong.",
             [](const GpuResult& r) { return std::to_string(r.host_link_bad_words); });
+    }
+    if (o.xcd_sweep) {
+      for (int clock = 0; clock < 2; ++clock) {
+        const char* name = clock ? "amdgpu_validate_xcd_clock_ghz" : "amdgpu_validate_xcd_rate";
+        p << "# HELP " << name
+          << (clock ? " Shader clock of one XCD during a level and mode of the XCD sweep.\n"
+                    : " Rate of one XCD in the XCD sweep: GB/s read and verified, GMFMA/s at level mfma.\n")
+          << "# TYPE " << name << " gauge\n";
+        for (auto& r : res)
+          for (auto& c : r.xcd_cells)
+            for (auto& row : c.sum.rows)
+              p << name << "{gpu=\"" << r.device << "\",xcd=\"" << row.xcd << "\",level=\""
+                << ntm::xcs::level_name(c.sum.level) << "\",mode=\"" << ntm::xcs::mode_name(c.sum.mode)
+                << "\"} " << jnum(clock ? row.clock_ghz : row.rate) << "\n";
+      }
     }
     if (o.mx_check) {
       auto gauge = [&](const char* name, const char* help, auto value) {
@@ -2059,6 +2232,33 @@ int main(int argc, char** argv) {
             ",\"mx_scale_spread\":" + std::to_string(r.mx_scale_spread) +
             ",\"mx_s\":" + jnum(r.mx_s);
     }
+    if (r.xcd_ran) {
+      namespace xs = ntm::xcs;
+      js += ",\"xcd_sweep_xcds\":" + std::to_string(r.xcd_xcds) +
+            ",\"xcd_sweep_mib\":" + std::to_string(o.xcd_sweep_mib) +
+            ",\"xcd_sweep_ratio\":" + jnum(o.xcd_ratio);
+      std::string slow = "[", bad = "[", rule;
+      for (auto& c : r.xcd_cells) {
+        const std::string k = std::string(",\"xcd_sweep_") + xs::level_name(c.sum.level) + "_" +
+                              xs::mode_name(c.sum.mode);
+        js += k + "_rate\":" + xs::rates_json(c.sum) + k + "_clock_ghz\":" + xs::clocks_json(c.sum) +
+              k + "_min_over_median\":" + jnum(c.sum.min_over_median) +
+              k + "_median\":" + jnum(c.sum.median_rate) +
+              k + "_passes\":" + std::to_string(c.passes) +
+              k + "_span_us\":[" + jnum((double)c.min_span_ticks * 0.01) + "," +
+              jnum((double)c.max_span_ticks * 0.01) + "]" +
+              k + "_gated\":" + (c.gated ? "true" : "false");
+        const std::string at = std::string(",\"level\":") + jstr(xs::level_name(c.sum.level)) +
+                               ",\"mode\":" + jstr(xs::mode_name(c.sum.mode)) + "}";
+        for (uint32_t x : c.sum.slow) slow += std::string(slow.size() > 1 ? "," : "") + "{\"xcd\":" + std::to_string(x) + at;
+        for (uint32_t x : c.sum.bad) bad += std::string(bad.size() > 1 ? "," : "") + "{\"xcd\":" + std::to_string(x) + at;
+        if (c.gated && !c.sum.rule_ran) rule = c.sum.rule_skipped;
+      }
+      js += ",\"xcd_sweep_slow\":" + slow + "],\"xcd_sweep_bad\":" + bad + "]" +
+            ",\"xcd_sweep_rule_skipped\":" + jstr(rule) + ",\"xcd_sweep_failures\":[";
+      for (size_t i = 0; i < r.xcd_failures.size(); ++i) js += (i ? "," : "") + jstr(r.xcd_failures[i]);
+      js += "],\"xcd_sweep_s\":" + jnum(r.xcd_s);
+    }
     js += "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(rccl_rows);
@@ -2101,7 +2301,15 @@ int main(int argc, char** argv) {
                     (node.empty() ? std::string() : ",\"node\":" + jstr(node)) +
                     ",\"n_gpus\":" + std::to_string(n) + ",\"gemm_tflops_aggregate\":" + jnum(agg) +
                     ",\"rccl_peak_busbw_GBps\":" + jnum(peak_rccl) +
-                    ",\"seconds\":" + jnum(t_end - t_start) + ",\"failures\":[";
+                    ",\"seconds\":" + jnum(t_end - t_start);
+    if (o.xcd_sweep) {  // the lowest min / median of a gated cell over all GPUs
+      double worst = 1e300;
+      for (auto& r : res)
+        for (auto& c : r.xcd_cells)
+          if (c.gated) worst = std::min(worst, c.sum.min_over_median);
+      t += ",\"xcd_sweep_min_over_median\":" + (worst < 1e300 ? jnum(worst) : std::string("null"));
+    }
+    t += ",\"failures\":[";
     for (size_t i = 0; i < g_failures.size() && t.size() < 3500; ++i)
       t += (i ? "," : "") + jstr(g_failures[i].substr(0, 200));
     t += "]}";
