@@ -27,125 +27,152 @@ class NativeLibraryMissing(RuntimeError):
     pass
 
 
-def _declare(lib: ctypes.CDLL) -> None:
-    c_int, c_size, c_float, c_vp = ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_void_p
-    sig = {
-        "ntm_version": ([], ctypes.c_char_p),
-        "ntm_gemm_shape_ok": ([c_int, c_int, c_int], c_int),
-        "ntm_gemm_bf16": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_gemm_bf16_variant": (
-            [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_gemm_fp8": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_gemm_fp8_shape_ok": ([c_int, c_int, c_int], c_int),
-        "ntm_gemm_fp8_variant": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_vp], c_int),
-        "ntm_k1_fp8_plan": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
-        "ntm_k1_fp8_plan_splitk": ([c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp], c_int),
-        "ntm_fp8_splitk_ws_bytes": ([c_int, c_int, c_int, c_int], c_size),
-        "ntm_gemm_fp8_splitk": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
-                                 c_int, c_vp, c_size, c_vp], c_int),
-        "ntm_gemm_fp8_ex": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                             c_size, c_vp], c_int),
-        "ntm_gemm_bf16_rowsum": (
-            [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_abft_check": ([c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+# The ctypes view of the C ABI that validation/include/ntm/abi.h declares: name ->
+# (argument types, result type). Module-level tables, readable without a built
+# library; tests/test_abi_header.py holds them to the header. SIGNATURES is what
+# this module binds on load, XGMI_SIGNATURES what parallel/xgmi.py adds for C2.
+c_int, c_size, c_float, c_vp = ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_void_p
+c_uint, c_u64, c_double = ctypes.c_uint, ctypes.c_ulonglong, ctypes.c_double
+_c_vpp = ctypes.POINTER(c_vp)
+
+SIGNATURES = {
+    "ntm_version": ([], ctypes.c_char_p),
+    "ntm_gemm_shape_ok": ([c_int, c_int, c_int], c_int),
+    "ntm_gemm_bf16": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_gemm_bf16_variant": (
+        [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_gemm_fp8": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_gemm_fp8_shape_ok": ([c_int, c_int, c_int], c_int),
+    "ntm_gemm_fp8_variant": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_vp], c_int),
+    "ntm_k1_fp8_plan": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
+    "ntm_k1_fp8_plan_splitk": ([c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp], c_int),
+    "ntm_fp8_splitk_ws_bytes": ([c_int, c_int, c_int, c_int], c_size),
+    "ntm_gemm_fp8_splitk": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                             c_int, c_vp, c_size, c_vp], c_int),
+    "ntm_gemm_fp8_ex": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                         c_size, c_vp], c_int),
+    "ntm_gemm_bf16_rowsum": (
+        [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_abft_check": ([c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                        c_vp, c_vp, c_vp], c_int),
+    "ntm_abft_result_bytes": ([], c_int),
+    "ntm_gemm_fp8_rowsum": (
+        [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_abft_check_fp8": ([c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
                             c_vp, c_vp, c_vp], c_int),
-        "ntm_abft_result_bytes": ([], c_int),
-        "ntm_gemm_fp8_rowsum": (
-            [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_abft_check_fp8": ([c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                c_vp, c_vp, c_vp], c_int),
-        "ntm_fill_uniform_bf16": ([c_vp, c_size, ctypes.c_ulonglong, c_float, c_vp], c_int),
-        "ntm_k1_plan": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
-        "ntm_k1_plan_splitk": ([c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp], c_int),
-        "ntm_gemm_bf16_ex": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                              c_size, c_vp], c_int),
-        "ntm_splitk_ws_bytes": ([c_int, c_int, c_int, c_int], c_size),
-        "ntm_sk_ws_bytes": ([c_int, c_int, c_int], c_size),
-        "ntm_skh_ws_bytes": ([c_int, c_int, c_int, c_int], c_size),
-        "ntm_gemm_bf16_skh": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                               c_vp, c_size, c_vp], c_int),
-        "ntm_k1_plan_times": ([c_int, c_int, c_int, c_vp, c_vp], c_int),
-        "ntm_gemm_bf16_sk": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                              c_size, c_vp], c_int),
-        "ntm_gemm_bf16_splitk": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
-                                  c_int, c_int, c_vp, c_size, c_vp], c_int),
-        "ntm_fill_uniform_e4m3": ([c_vp, c_size, ctypes.c_ulonglong, c_float, c_vp], c_int),
-        "ntm_ref_gemm_f32_e4m3": (
-            [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_ref_gemm_f32": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_verify_bf16": ([c_vp, c_vp, c_size, c_float, c_float, c_vp, c_vp], c_int),
-        "ntm_verify_result_bytes": ([], c_int),
-        "ntm_clock_probe": ([c_int, c_int, c_vp, c_vp, c_vp], c_int),
-        "ntm_gemm_bf16_clock_grid": ([c_int, c_int], c_int),
-        "ntm_gemm_bf16_clock_words": ([], c_int),
-        "ntm_sk_error_word_index": ([], c_int),
-        "ntm_set_sk_fault_inject": ([c_int], None),
-        "ntm_gemm_bf16_skh_ex": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_vp, c_size, c_int, c_vp], c_int),
-        "ntm_plan_cus": ([], c_int),
-        "ntm_set_cus_override": ([c_int], None),
-        "ntm_set_plan_pp_tiles": ([c_int], None),
-        "ntm_set_plan_splitk": ([ctypes.c_double, c_int, c_int], None),
-        "ntm_set_plan_splitk_ragged": ([c_int], None),
-        "ntm_pp3h_vmcnt": ([c_int, c_int, c_int], c_int),
-        "ntm_gemm_bf16_clock": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-                                 c_vp], c_int),
-        "ntm_stream_copy": ([c_vp, c_vp, c_size, c_vp], c_int),
-        "ntm_stream_read": ([c_vp, c_size, c_vp, c_vp], c_int),
-        "ntm_stream_copy_ex": ([c_vp, c_vp, c_size, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_stream_read_ex": ([c_vp, c_size, c_vp, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_hbm_pattern_write": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
+    "ntm_fill_uniform_bf16": ([c_vp, c_size, c_u64, c_float, c_vp], c_int),
+    "ntm_k1_plan": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
+    "ntm_k1_plan_splitk": ([c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp], c_int),
+    "ntm_gemm_bf16_ex": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                          c_size, c_vp], c_int),
+    "ntm_splitk_ws_bytes": ([c_int, c_int, c_int, c_int], c_size),
+    "ntm_sk_ws_bytes": ([c_int, c_int, c_int], c_size),
+    "ntm_skh_ws_bytes": ([c_int, c_int, c_int, c_int], c_size),
+    "ntm_gemm_bf16_skh": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                           c_vp, c_size, c_vp], c_int),
+    "ntm_k1_plan_times": ([c_int, c_int, c_int, c_vp, c_vp], c_int),
+    "ntm_gemm_bf16_sk": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                          c_size, c_vp], c_int),
+    "ntm_gemm_bf16_splitk": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                              c_int, c_int, c_vp, c_size, c_vp], c_int),
+    "ntm_fill_uniform_e4m3": ([c_vp, c_size, c_u64, c_float, c_vp], c_int),
+    "ntm_ref_gemm_f32_e4m3": (
+        [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_ref_gemm_f32": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_verify_bf16": ([c_vp, c_vp, c_size, c_float, c_float, c_vp, c_vp], c_int),
+    "ntm_verify_result_bytes": ([], c_int),
+    "ntm_clock_probe": ([c_int, c_int, c_vp, c_vp, c_vp], c_int),
+    "ntm_gemm_bf16_clock_grid": ([c_int, c_int], c_int),
+    "ntm_gemm_bf16_clock_words": ([], c_int),
+    "ntm_sk_error_word_index": ([], c_int),
+    "ntm_set_sk_fault_inject": ([c_int], None),
+    "ntm_gemm_bf16_skh_ex": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_vp, c_size, c_int, c_vp], c_int),
+    "ntm_plan_cus": ([], c_int),
+    "ntm_set_cus_override": ([c_int], None),
+    "ntm_set_plan_pp_tiles": ([c_int], None),
+    "ntm_set_plan_splitk": ([c_double, c_int, c_int], None),
+    "ntm_set_plan_splitk_ragged": ([c_int], None),
+    "ntm_pp3h_vmcnt": ([c_int, c_int, c_int], c_int),
+    "ntm_gemm_bf16_clock": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                             c_vp], c_int),
+    "ntm_stream_copy": ([c_vp, c_vp, c_size, c_vp], c_int),
+    "ntm_stream_read": ([c_vp, c_size, c_vp, c_vp], c_int),
+    "ntm_stream_copy_ex": ([c_vp, c_vp, c_size, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_stream_read_ex": ([c_vp, c_size, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_hbm_pattern_write": ([c_vp, c_size, c_u64, c_int, c_u64, c_int,
+                               c_vp], c_int),
+    "ntm_hbm_pattern_verify": ([c_vp, c_size, c_u64, c_int, c_u64, c_int,
+                                c_int, c_vp, c_vp], c_int),
+    "ntm_hbm_pattern_result_bytes": ([], c_int),
+    "ntm_host_link_default_blocks": ([c_int], c_int),
+    "ntm_host_link_tile_bytes": ([c_int], c_int),
+    "ntm_host_link_push": ([c_vp, c_size, c_u64, c_int, c_u64, c_int,
+                            c_int, c_vp], c_int),
+    "ntm_host_link_push_ex": ([c_vp, c_size, c_u64, c_int, c_u64, c_int,
+                               c_int, c_int, c_int, c_vp], c_int),
+    "ntm_host_link_pull": ([c_vp, c_size, c_u64, c_int, c_u64, c_int,
+                            c_vp, c_int, c_vp, c_vp], c_int),
+    "ntm_host_link_pull_ex": ([c_vp, c_size, c_u64, c_int, c_u64, c_int,
+                               c_vp, c_int, c_int, c_int, c_vp, c_vp], c_int),
+    "ntm_host_link_chase": ([c_vp, c_u64, c_u64, c_uint, c_vp,
+                             c_vp], c_int),
+    "ntm_host_link_clock_khz": ([c_int], c_int),
+    "ntm_mx_shape_ok": ([c_int, c_int, c_int], c_int),
+    "ntm_mx_gemm": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_mx_reference": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_mx_compare": ([c_vp, c_vp, c_size, c_vp, c_vp], c_int),
+    "ntm_mx_mismatch_bytes": ([], c_int),
+    "ntm_cu_sweep_record_bytes": ([], c_int),
+    "ntm_cu_sweep_expected_bytes": ([c_int], c_size),
+    "ntm_cu_sweep_expected": ([c_int, c_uint, c_vp, c_size], c_int),
+    "ntm_cu_sweep_lds_words": ([c_uint, c_uint, c_uint, c_uint, c_vp],
+                               c_int),
+    "ntm_cu_sweep_max_lds_bytes": ([c_int], c_int),
+    "ntm_cu_sweep_launch": ([c_vp, c_vp, c_uint, c_int, c_size, c_uint,
+                             c_uint, c_int, c_vp], c_int),
+    "ntm_cu_sweep_decode": ([c_uint, c_uint, c_vp], None),
+    "ntm_cu_sweep_summarize": ([c_vp, c_size, c_uint, c_uint, c_int, c_vp, c_size],
+                               c_size),
+    "ntm_xcd_sweep_record_bytes": ([], c_int),
+    "ntm_xcd_sweep_heads_bytes": ([], c_int),
+    "ntm_xcd_sweep_tile_bytes": ([], c_int),
+    "ntm_xcd_sweep_mfma_per_batch": ([], c_int),
+    "ntm_xcd_sweep_gated": ([c_int, c_int], c_int),
+    "ntm_xcd_sweep_read_launch": ([c_vp, c_size, c_uint, c_uint, c_uint, c_int,
+                                   c_u64, c_uint, c_int, c_uint, c_vp, c_vp,
                                    c_vp], c_int),
-        "ntm_hbm_pattern_verify": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
-                                    c_int, c_vp, c_vp], c_int),
-        "ntm_hbm_pattern_result_bytes": ([], c_int),
-        "ntm_host_link_default_blocks": ([c_int], c_int),
-        "ntm_host_link_tile_bytes": ([c_int], c_int),
-        "ntm_host_link_push": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
-                                c_int, c_vp], c_int),
-        "ntm_host_link_push_ex": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
-                                   c_int, c_int, c_int, c_vp], c_int),
-        "ntm_host_link_pull": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
-                                c_vp, c_int, c_vp, c_vp], c_int),
-        "ntm_host_link_pull_ex": ([c_vp, c_size, ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int,
-                                   c_vp, c_int, c_int, c_int, c_vp, c_vp], c_int),
-        "ntm_host_link_chase": ([c_vp, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_vp,
-                                 c_vp], c_int),
-        "ntm_host_link_clock_khz": ([c_int], c_int),
-        "ntm_mx_shape_ok": ([c_int, c_int, c_int], c_int),
-        "ntm_mx_gemm": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_mx_reference": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
-        "ntm_mx_compare": ([c_vp, c_vp, c_size, c_vp, c_vp], c_int),
-        "ntm_mx_mismatch_bytes": ([], c_int),
-        "ntm_cu_sweep_record_bytes": ([], c_int),
-        "ntm_cu_sweep_expected_bytes": ([c_int], c_size),
-        "ntm_cu_sweep_expected": ([c_int, ctypes.c_uint, c_vp, c_size], c_int),
-        "ntm_cu_sweep_lds_words": ([ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_vp],
-                                   c_int),
-        "ntm_cu_sweep_max_lds_bytes": ([c_int], c_int),
-        "ntm_cu_sweep_launch": ([c_vp, c_vp, ctypes.c_uint, c_int, c_size, ctypes.c_uint,
-                                 ctypes.c_uint, c_int, c_vp], c_int),
-        "ntm_cu_sweep_decode": ([ctypes.c_uint, ctypes.c_uint, c_vp], None),
-        "ntm_cu_sweep_summarize": ([c_vp, c_size, ctypes.c_uint, ctypes.c_uint, c_int, c_vp, c_size],
-                                   c_size),
-        "ntm_xcd_sweep_record_bytes": ([], c_int),
-        "ntm_xcd_sweep_heads_bytes": ([], c_int),
-        "ntm_xcd_sweep_tile_bytes": ([], c_int),
-        "ntm_xcd_sweep_mfma_per_batch": ([], c_int),
-        "ntm_xcd_sweep_gated": ([c_int, c_int], c_int),
-        "ntm_xcd_sweep_read_launch": ([c_vp, c_size, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, c_int,
-                                       ctypes.c_ulonglong, ctypes.c_uint, c_int, ctypes.c_uint, c_vp, c_vp,
-                                       c_vp], c_int),
-        "ntm_xcd_sweep_mfma_launch": ([ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint,
-                                       ctypes.c_uint, c_int, ctypes.c_uint, c_vp, c_vp, c_vp], c_int),
-        "ntm_xcd_sweep_summarize": ([c_vp, c_size, c_int, c_int, ctypes.c_uint, ctypes.c_uint,
-                                     ctypes.c_ulonglong, ctypes.c_double, c_int, c_vp, c_size], c_size),
-    }
-    for name, (argt, rest) in sig.items():
+    "ntm_xcd_sweep_mfma_launch": ([c_uint, c_uint, c_uint, c_uint,
+                                   c_uint, c_int, c_uint, c_vp, c_vp, c_vp], c_int),
+    "ntm_xcd_sweep_summarize": ([c_vp, c_size, c_int, c_int, c_uint, c_uint,
+                                 c_u64, c_double, c_int, c_vp, c_size], c_size),
+}
+
+XGMI_SIGNATURES = {
+    "ntm_xgmi_allreduce_bf16": ([_c_vpp, _c_vpp, _c_vpp, c_int, c_int, c_int, c_int, c_size,
+                                 c_uint, c_vp, c_int, c_vp], c_int),
+    "ntm_xgmi_allreduce_bf16_ex": ([_c_vpp, _c_vpp, _c_vpp, c_int, c_int, c_int, c_int, c_size,
+                                    c_uint, c_vp, c_int, c_uint, c_uint, c_vp], c_int),
+    "ntm_xgmi_signal_bytes": ([c_int], c_size),
+    "ntm_malloc": ([_c_vpp, c_size, c_int], c_int),
+    "ntm_free": ([c_vp], c_int),
+    "ntm_memset_async": ([c_vp, c_int, c_size, c_vp], c_int),
+    "ntm_ipc_handle": ([c_vp, c_vp], c_int),
+    "ntm_ipc_open": ([c_vp, _c_vpp], c_int),
+    "ntm_ipc_close": ([c_vp], c_int),
+}
+
+
+def declare(lib: ctypes.CDLL, signatures: dict) -> None:
+    for name, (argt, rest) in signatures.items():
         fn = getattr(lib, name)
         fn.argtypes = argt
         fn.restype = rest
+
+
+def _declare(lib: ctypes.CDLL) -> None:
+    declare(lib, SIGNATURES)
 
 
 def lib() -> ctypes.CDLL:
@@ -165,7 +192,6 @@ def lib() -> ctypes.CDLL:
 
 
 def _declare_experimental(lib: ctypes.CDLL) -> None:
-    c_int, c_vp, c_size = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
     gemm = [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]
     sig = {
         "ntm_experimental_version": ([], ctypes.c_char_p),
@@ -190,10 +216,7 @@ def _declare_experimental(lib: ctypes.CDLL) -> None:
         "ntm_gemm_bf16_pp6_stamp": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_vp, c_vp], c_int),
     }
-    for name, (argt, rest) in sig.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argt
-        fn.restype = rest
+    declare(lib, sig)
 
 
 def lib_experimental() -> ctypes.CDLL:

@@ -36,6 +36,11 @@ LIB_NAME = "libntm_validation.so"
 EXP_LIB_NAME = "libntm_experimental.so"
 # the shipping sources: the Job binary and libntm_validation.so link exactly these
 SHIPPING_SRCS = ("ntm_validation.hip", "xgmi_allreduce.hip")
+# the Job binary's own sources (validation/src/validate/README.md); collectives.hip
+# is the only one with device code
+BINARY_SRCS = ("validate/main.cpp", "validate/host.cpp", "validate/gpu.cpp", "validate/hbm_test.cpp",
+               "validate/cu_sweep.cpp", "validate/host_link.cpp", "validate/mx_check.cpp",
+               "validate/xcd_sweep.cpp", "validate/collectives.hip")
 BIN_NAME = "amdgpu-validate"
 
 COMMON_FLAGS = [
@@ -70,7 +75,8 @@ def _stale(target: Path, deps: list[Path]) -> bool:
 
 
 def _deps() -> list[Path]:
-    return sorted(INCLUDE.rglob("*.hpp")) + sorted(SRC.glob("*.hip")) + sorted(SRC.glob("*.cpp"))
+    return (sorted(INCLUDE.rglob("*.hpp")) + sorted(INCLUDE.rglob("*.h")) +
+            [p for pat in ("*.hip", "*.cpp", "*.hpp") for p in sorted(SRC.rglob(pat))])
 
 
 def _build_so(name: str, srcs: list[Path], force: bool, verbose: bool) -> Path:
@@ -101,14 +107,14 @@ ASAN_FLAGS = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=un
 
 def build_binary(force: bool = False, verbose: bool = True, asan: bool = False) -> Path:
     out = BUILD / (BIN_NAME + ("-asan" if asan else ""))
-    main = SRC / "validate_main.cpp"
-    if not main.exists():
+    own = [SRC / s for s in BINARY_SRCS]
+    if not all(p.exists() for p in own):
         return out
     if force or _stale(out, _deps()):
         BUILD.mkdir(parents=True, exist_ok=True)
-        srcs = [str(SRC / s) for s in SHIPPING_SRCS]
+        srcs = [str(p) for p in own] + [str(SRC / s) for s in SHIPPING_SRCS]
         cmd = [
-            hipcc(), *COMMON_FLAGS, *(ASAN_FLAGS if asan else []), "-x", "hip", str(main), *srcs,
+            hipcc(), *COMMON_FLAGS, *(ASAN_FLAGS if asan else []), "-x", "hip", *srcs,
             "-I/opt/rocm/include", "-L/opt/rocm/lib", "-lrccl", "-lpthread",
             "-Wl,-rpath,/opt/rocm/lib", "-o", str(out) + ".tmp",
         ]

@@ -175,7 +175,7 @@ def p2p_matrix(env: DistEnv, nbytes: int = 256 << 20, iters: int = 3) -> P2pMatr
     GPUs, gloo on CPU) while the other ranks wait at the barrier.
 
     This is the one-process-per-GPU counterpart of amdgpu-validate's C3 link
-    matrix (validation/src/validate_main.cpp ``run_p2p``): on a fully connected
+    matrix (validation/src/validate/collectives.hip ``run_p2p``): on a fully connected
     8x MI355X mesh every pair is one link, so a degraded link is one cell.
     Timed on the receiver between the pair's barrier and its last completed
     receive; the first message of each pair is checked element for element.

@@ -22,36 +22,14 @@ import time
 
 import torch
 
-from ..ops._lib import check, lib, stream_handle
+from ..ops._lib import XGMI_SIGNATURES, check, declare, lib, stream_handle
 
 MAX_RANKS = 8
 
 
 def _declare() -> ctypes.CDLL:
     L = lib()
-    c_int, c_size, c_vp = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
-    pp = ctypes.POINTER(c_vp)
-    L.ntm_xgmi_allreduce_bf16.argtypes = [pp, pp, pp, c_int, c_int, c_int, c_int, c_size,
-                                          ctypes.c_uint, c_vp, c_int, c_vp]
-    L.ntm_xgmi_allreduce_bf16.restype = c_int
-    L.ntm_xgmi_allreduce_bf16_ex.argtypes = [pp, pp, pp, c_int, c_int, c_int, c_int, c_size,
-                                             ctypes.c_uint, c_vp, c_int, ctypes.c_uint,
-                                             ctypes.c_uint, c_vp]
-    L.ntm_xgmi_allreduce_bf16_ex.restype = c_int
-    L.ntm_xgmi_signal_bytes.argtypes = [c_int]
-    L.ntm_xgmi_signal_bytes.restype = c_size
-    L.ntm_malloc.argtypes = [ctypes.POINTER(c_vp), c_size, c_int]
-    L.ntm_malloc.restype = c_int
-    L.ntm_free.argtypes = [c_vp]
-    L.ntm_free.restype = c_int
-    L.ntm_memset_async.argtypes = [c_vp, c_int, c_size, c_vp]
-    L.ntm_memset_async.restype = c_int
-    L.ntm_ipc_handle.argtypes = [c_vp, c_vp]
-    L.ntm_ipc_handle.restype = c_int
-    L.ntm_ipc_open.argtypes = [c_vp, ctypes.POINTER(c_vp)]
-    L.ntm_ipc_open.restype = c_int
-    L.ntm_ipc_close.argtypes = [c_vp]
-    L.ntm_ipc_close.restype = c_int
+    declare(L, XGMI_SIGNATURES)
     return L
 
 

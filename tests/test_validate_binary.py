@@ -1,4 +1,4 @@
-"""The standalone ``amdgpu-validate`` Job binary (validation/src/validate_main.cpp).
+"""The standalone ``amdgpu-validate`` Job binary (validation/src/validate/).
 
 CPU tests cover argument handling and the no-GPU environment error (exit 2);
 GPU tests run the real checks on one MI355X, including native fault injection

@@ -40,12 +40,13 @@
 // writes only touch slices no peer reads before the next barrier.
 #pragma once
 
+#include "ntm/abi.h"
 #include "ntm/common.hpp"
 
 namespace ntm {
 namespace xgmi {
 
-constexpr int kMaxRanks = 8;
+constexpr int kMaxRanks = NTM_XGMI_MAX_RANKS;  // 8; host code takes it from ntm/abi.h
 constexpr int kThreads = 256;
 constexpr int kPhases = 3;                 // entry, reduce-scatter done, exit
 // Default spin limits (s_sleep 2 + one uncached load per spin). The ENTRY

@@ -36,7 +36,7 @@
 #include "ntm/mx_gemm.hpp"
 #include "ntm/stream_policy_exp.hpp"
 
-#define NTM_API extern "C" __attribute__((visibility("default")))
+#include "ntm/abi.h"  // NTM_API; this file's own exports are for tests only and are declared here
 
 namespace {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }

@@ -28,7 +28,7 @@
 #include "ntm/mx_gemm.hpp"
 #include "ntm/xcd_sweep.hpp"
 
-#define NTM_API extern "C" __attribute__((visibility("default")))
+#include "ntm/abi.h"  // NTM_API and the prototype of every export below
 
 namespace {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }

@@ -1,7 +1,7 @@
 // C ABI for C2, the hand-written xGMI all-reduce (see ntm/xgmi_allreduce.hpp).
 #include "ntm/xgmi_allreduce.hpp"
 
-#define NTM_API extern "C" __attribute__((visibility("default")))
+#include "ntm/abi.h"  // NTM_API and the prototype of every export below
 
 // in_ptrs/out_ptrs/sig_ptrs: host arrays of `nranks` device pointers (peer-
 // accessible from the launching device). Launches ranks rank_base ..
