@@ -363,6 +363,12 @@ variable "validation_xcd_ratio" {
   }
 }
 
+variable "validation_atomics_check" {
+  type        = bool
+  default     = false
+  description = "Run the Job's atomics and cross-XCD hand-off check (K9): every kind of global atomic (integer add / and / or / xor / min / max, compare-and-swap, fp32 / fp64 / packed bf16 / packed fp16 add) on a table whose exact answer a kernel without atomics computes, a ticket draw in which every ticket must be handed out exactly once, and plain stores handed from one XCD to another under agent-scope release / acquire with every word compared. A wrong slot, a lost ticket or a stale word fails the Job by op and slot, head and ticket, or reader and writer XCD; rates are reported. It sets NTM_ATOMICS_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/atomics/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

@@ -20,6 +20,9 @@ K7 ``mx_gemm``, ``mx_reference_gpu``, ``mx_compare`` - a block-scaled GEMM in th
    ``mx_make_inputs``, ``mx_dense_exact`` - the host side (numpy, ``ops.mx``).
 K8 ``xcd_sweep_read``, ``xcd_sweep_mfma``, ``xcd_sweep_summarize`` - a verified read and an
    MFMA clock probe per XCD, each XCD timed against its own stamps.
+K9 ``atomics_rmw``, ``atomics_rmw_reference``, ``atomics_tickets``, ``atomics_handoff``,
+   ``atomics_summarize`` - every kind of global atomic with a checked answer, and plain stores
+   handed from one XCD to another under agent-scope release / acquire.
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -92,6 +95,15 @@ from .kernels import (  # noqa: F401
     xcd_sweep_record_dtype,
     xcd_sweep_summarize,
     xcd_sweep_xcds,
+    ATOMIC_OPS,
+    atomics_exact,
+    atomics_handoff,
+    atomics_record_dtype,
+    atomics_rmw,
+    atomics_rmw_expected,
+    atomics_rmw_reference,
+    atomics_summarize,
+    atomics_tickets,
     verify_bf16,
 )
 from .mx import (  # noqa: F401

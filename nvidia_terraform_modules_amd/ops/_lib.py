@@ -147,6 +147,24 @@ SIGNATURES = {
                                    c_uint, c_int, c_uint, c_vp, c_vp, c_vp], c_int),
     "ntm_xcd_sweep_summarize": ([c_vp, c_size, c_int, c_int, c_uint, c_uint,
                                  c_u64, c_double, c_int, c_vp, c_size], c_size),
+    "ntm_atomics_ops": ([], c_int),
+    "ntm_atomics_op_name": ([c_int], ctypes.c_char_p),
+    "ntm_atomics_slot_bytes": ([c_int], c_int),
+    "ntm_atomics_record_bytes": ([], c_int),
+    "ntm_atomics_exact": ([c_int, c_u64, c_u64], c_int),
+    "ntm_atomics_rmw_shape_ok": ([c_int, c_u64, c_uint, c_uint, c_u64], c_int),
+    "ntm_atomics_expected": ([c_int, c_u64, c_u64, c_u64, c_u64, c_vp], c_int),
+    "ntm_atomics_rmw_launch": ([c_int, c_vp, c_u64, c_uint, c_uint, c_u64, c_u64, c_vp], c_int),
+    "ntm_atomics_rmw_reference_launch": ([c_int, c_vp, c_u64, c_uint, c_uint, c_u64, c_u64, c_vp], c_int),
+    "ntm_atomics_ticket_claim_bytes": ([c_uint, c_uint, c_uint], c_size),
+    "ntm_atomics_counter_bytes": ([c_uint], c_size),
+    "ntm_atomics_ticket_launch": ([c_vp, c_vp, c_uint, c_uint, c_uint, c_uint, c_vp], c_int),
+    "ntm_atomics_handoff_slab_bytes": ([c_uint, c_uint], c_size),
+    "ntm_atomics_handoff_init": ([c_vp, c_uint, c_uint, c_u64, c_uint, c_vp], c_int),
+    "ntm_atomics_handoff_launch": ([c_vp, c_vp, c_vp, c_uint, c_uint, c_u64, c_uint, c_uint, c_vp], c_int),
+    "ntm_atomics_summarize_rmw": ([c_int, c_vp, c_vp, c_u64, c_int, c_vp, c_size], c_size),
+    "ntm_atomics_summarize_tickets": ([c_vp, c_vp, c_uint, c_uint, c_uint, c_int, c_vp, c_size], c_size),
+    "ntm_atomics_summarize_handoff": ([c_vp, c_size, c_uint, c_uint, c_uint, c_uint, c_int, c_vp, c_size], c_size),
 }
 
 XGMI_SIGNATURES = {

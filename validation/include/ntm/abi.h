@@ -139,6 +139,26 @@ NTM_API int ntm_xcd_sweep_read_launch(const void* buf, size_t slice_bytes, unsig
 NTM_API int ntm_xcd_sweep_mfma_launch(unsigned grid, unsigned batches, unsigned seed, unsigned xcds, unsigned xcd_mask, int slow_xcd, unsigned slow_factor, void* records, float* sink, void* stream);
 NTM_API size_t ntm_xcd_sweep_summarize(const void* records, size_t n, int level, int mode, unsigned xcds, unsigned mask, unsigned long long expected_tiles, double ratio, int gpu, char* json, size_t cap);
 
+/* ---- K9 atomics and cross-XCD hand-off check (ntm/atomics.hpp, ntm/atomics_plan.hpp) */
+NTM_API int ntm_atomics_ops(void);
+NTM_API const char* ntm_atomics_op_name(int op);
+NTM_API int ntm_atomics_slot_bytes(int op);
+NTM_API int ntm_atomics_record_bytes(void);
+NTM_API int ntm_atomics_exact(int op, unsigned long long adds_per_slot, unsigned long long max_abs);
+NTM_API int ntm_atomics_rmw_shape_ok(int op, unsigned long long slots, unsigned grid, unsigned iters, unsigned long long max_abs);
+NTM_API int ntm_atomics_expected(int op, unsigned long long slots, unsigned long long total, unsigned long long seed, unsigned long long max_abs, void* out);
+NTM_API int ntm_atomics_rmw_launch(int op, void* table, unsigned long long slots, unsigned grid, unsigned iters, unsigned long long seed, unsigned long long max_abs, void* stream);
+NTM_API int ntm_atomics_rmw_reference_launch(int op, void* table, unsigned long long slots, unsigned grid, unsigned iters, unsigned long long seed, unsigned long long max_abs, void* stream);
+NTM_API size_t ntm_atomics_ticket_claim_bytes(unsigned heads, unsigned grid, unsigned iters);
+NTM_API size_t ntm_atomics_counter_bytes(unsigned counters);
+NTM_API int ntm_atomics_ticket_launch(void* counters, void* claim, unsigned heads, unsigned grid, unsigned iters, unsigned inject_gid, void* stream);
+NTM_API size_t ntm_atomics_handoff_slab_bytes(unsigned episodes, unsigned episode_size);
+NTM_API int ntm_atomics_handoff_init(void* slabs, unsigned episodes, unsigned episode_size, unsigned long long seed, unsigned round, void* stream);
+NTM_API int ntm_atomics_handoff_launch(void* slabs, void* counters, void* records, unsigned episodes, unsigned episode_size, unsigned long long seed, unsigned round, unsigned inject_wg, void* stream);
+NTM_API size_t ntm_atomics_summarize_rmw(int op, const void* got, const void* expected, unsigned long long slots, int gpu, char* json, size_t cap);
+NTM_API size_t ntm_atomics_summarize_tickets(const void* counters, const void* claim, unsigned heads, unsigned grid, unsigned iters, int gpu, char* json, size_t cap);
+NTM_API size_t ntm_atomics_summarize_handoff(const void* records, size_t n, unsigned episodes, unsigned episode_size, unsigned xcds, unsigned launches, int gpu, char* json, size_t cap);
+
 /* ---- C2 hand-written xGMI all-reduce (xgmi_allreduce.hip, ntm/xgmi_allreduce.hpp)
  * and the allocation / HIP IPC helpers its Python side needs */
 NTM_API int ntm_xgmi_allreduce_bf16(const void* const* in_ptrs, void* const* out_ptrs, unsigned* const* sig_ptrs, int nranks, int rank_base, int nranks_here, int nblk, size_t count, unsigned epoch, unsigned* err, int one_shot, void* stream);

@@ -1,6 +1,7 @@
 // C ABI over the MI355X validation kernels (K1 GEMM, K2 HBM stream,
 // K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep,
-// K6 host-link check, K7 MX block-scaled matrix check, K8 per-XCD sweep).
+// K6 host-link check, K7 MX block-scaled matrix check, K8 per-XCD sweep,
+// K9 atomics and cross-XCD hand-off check).
 // Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
@@ -12,6 +13,7 @@
 // the 256x256 kernel and the wave-specialised tiles, K2, K3).
 // The non-default K1 builds, schedule knobs and diagnostics live in
 // ntm_experimental.hip -> libntm_experimental.so (tests and tools only).
+#include "ntm/atomics.hpp"
 #include "ntm/aux_kernels.hpp"
 #include "ntm/cu_sweep.hpp"
 #include "ntm/gemm_bf16_pp2.hpp"
@@ -1061,4 +1063,95 @@ NTM_API size_t ntm_xcd_sweep_summarize(const void* records, size_t n, int level,
       ntm::xcs::summarize(recs.data(), n, level, mode, xcds, mask, expected_tiles, ratio, gpu));
   if (json && j.size() < cap) std::memcpy(json, j.c_str(), j.size() + 1);
   return j.size();
+}
+
+// K9: atomics and cross-XCD hand-off check (atomics.hpp; ops, operands, bounds, records
+// and verdicts in atomics_plan.hpp). rmw: `table` is slots x ntm_atomics_slot_bytes(op)
+// device bytes, initialised here; the reference launch fills a second table with no
+// atomic. tickets: `counters` (ntm_atomics_counter_bytes(heads)) and `claim`
+// (ntm_atomics_ticket_claim_bytes) are initialised here. handoff: `slabs` hold round - 1
+// (ntm_atomics_handoff_init, or the round before), `counters` one line per episode,
+// `records` grid x 96 bytes, every one written. inject_gid / inject_wg = ~0u: none.
+namespace atm = ntm::atm;
+NTM_API int ntm_atomics_ops() { return atm::kOps; }
+NTM_API const char* ntm_atomics_op_name(int op) { return atm::op_name(op); }
+NTM_API int ntm_atomics_slot_bytes(int op) { return op >= 0 && op < atm::kOps ? (int)atm::slot_bytes(op) : 0; }
+NTM_API int ntm_atomics_record_bytes() { return (int)sizeof(atm::Record); }
+NTM_API int ntm_atomics_exact(int op, unsigned long long adds_per_slot, unsigned long long max_abs) {
+  return atm::atomics_exact(op, adds_per_slot, max_abs) ? 1 : 0;
+}
+NTM_API int ntm_atomics_rmw_shape_ok(int op, unsigned long long slots, unsigned grid, unsigned iters,
+                                     unsigned long long max_abs) {
+  return atm::rmw_shape_ok(op, slots, grid, iters, max_abs) ? 1 : 0;
+}
+// Host-only: the expected table, slots x slot_bytes(op), into `out`. 0 = written.
+NTM_API int ntm_atomics_expected(int op, unsigned long long slots, unsigned long long total, unsigned long long seed,
+                                 unsigned long long max_abs, void* out) {
+  if (op < 0 || op >= atm::kOps || !slots || !out || (atm::is_float(op) && !max_abs)) return 1;
+  for (unsigned long long s = 0; s < slots; ++s) {
+    const uint64_t v = atm::expected_slot(op, s, slots, total, seed, atm::is_float(op) ? max_abs : 1);
+    if (atm::slot_bytes(op) == 8) ((uint64_t*)out)[s] = v;
+    else ((uint32_t*)out)[s] = (uint32_t)v;
+  }
+  return 0;
+}
+NTM_API int ntm_atomics_rmw_launch(int op, void* table, unsigned long long slots, unsigned grid, unsigned iters,
+                                   unsigned long long seed, unsigned long long max_abs, void* stream) {
+  return (int)atm::launch_rmw(op, table, slots, grid, iters, seed, max_abs, S(stream));
+}
+NTM_API int ntm_atomics_rmw_reference_launch(int op, void* table, unsigned long long slots, unsigned grid,
+                                             unsigned iters, unsigned long long seed, unsigned long long max_abs,
+                                             void* stream) {
+  return (int)atm::launch_rmw_reference(op, table, slots, grid, iters, seed, max_abs, S(stream));
+}
+NTM_API size_t ntm_atomics_ticket_claim_bytes(unsigned heads, unsigned grid, unsigned iters) {
+  return atm::ticket_shape_ok(heads, grid, iters) ? (size_t)(heads * atm::tickets_per_head(heads, grid, iters) * 4) : 0;
+}
+NTM_API size_t ntm_atomics_counter_bytes(unsigned counters) { return (size_t)counters * atm::kLineWords * 4; }
+NTM_API int ntm_atomics_ticket_launch(void* counters, void* claim, unsigned heads, unsigned grid, unsigned iters,
+                                      unsigned inject_gid, void* stream) {
+  return (int)atm::launch_tickets((uint32_t*)counters, (uint32_t*)claim, heads, grid, iters, inject_gid, S(stream));
+}
+NTM_API size_t ntm_atomics_handoff_slab_bytes(unsigned episodes, unsigned episode_size) {
+  return atm::handoff_shape_ok(episodes, episode_size) ? atm::handoff_slab_bytes(episodes, episode_size) : 0;
+}
+NTM_API int ntm_atomics_handoff_init(void* slabs, unsigned episodes, unsigned episode_size, unsigned long long seed,
+                                     unsigned round, void* stream) {
+  return (int)atm::launch_handoff_init(slabs, episodes, episode_size, seed, round, S(stream));
+}
+NTM_API int ntm_atomics_handoff_launch(void* slabs, void* counters, void* records, unsigned episodes,
+                                       unsigned episode_size, unsigned long long seed, unsigned round,
+                                       unsigned inject_wg, void* stream) {
+  return (int)atm::launch_handoff(slabs, (uint32_t*)counters, (atm::Record*)records, episodes, episode_size, seed,
+                                  round, inject_wg, S(stream));
+}
+
+// Host-only verdicts as JSON (atomics_plan.hpp). Each returns the JSON's length; it is
+// written (NUL-terminated) only when it fits in `cap`. 0 = arguments refused.
+namespace {
+size_t put_json(const std::string& j, char* json, size_t cap) {
+  if (json && j.size() < cap) std::memcpy(json, j.c_str(), j.size() + 1);
+  return j.size();
+}
+}  // namespace
+NTM_API size_t ntm_atomics_summarize_rmw(int op, const void* got, const void* expected, unsigned long long slots,
+                                         int gpu, char* json, size_t cap) {
+  if (op < 0 || op >= atm::kOps || !got || !expected) return 0;
+  return put_json(atm::rmw_json(atm::summarize_rmw(op, got, expected, slots, gpu)), json, cap);
+}
+NTM_API size_t ntm_atomics_summarize_tickets(const void* counters, const void* claim, unsigned heads, unsigned grid,
+                                             unsigned iters, int gpu, char* json, size_t cap) {
+  if (!counters || !claim || !atm::ticket_shape_ok(heads, grid, iters)) return 0;
+  return put_json(atm::ticket_json(atm::summarize_tickets((const uint32_t*)counters, (const uint32_t*)claim, heads,
+                                                          atm::tickets_per_head(heads, grid, iters),
+                                                          grid * atm::kThreads, iters, gpu)),
+                  json, cap);
+}
+NTM_API size_t ntm_atomics_summarize_handoff(const void* records, size_t n, unsigned episodes, unsigned episode_size,
+                                             unsigned xcds, unsigned launches, int gpu, char* json, size_t cap) {
+  if (!atm::handoff_shape_ok(episodes, episode_size) || xcds < 1 || launches < 1) return 0;
+  std::vector<atm::Record> recs(n);
+  if (n) std::memcpy(recs.data(), records, n * sizeof(atm::Record));
+  return put_json(atm::handoff_json(atm::summarize_handoff(recs.data(), n, episodes, episode_size, xcds, launches, gpu)),
+                  json, cap);
 }

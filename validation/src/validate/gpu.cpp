@@ -267,6 +267,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   if (o.host_link_mib > 0 && !run_host_link(g, r.host_link)) return false;
   if (o.mx_check && !run_mx_check(g, r.mx)) return false;
   if (o.xcd_sweep && !run_xcd_sweep(g, r.xcd)) return false;
+  if (o.atomics_check && !run_atomics(g, r.atomics)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));

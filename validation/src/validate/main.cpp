@@ -18,6 +18,9 @@
 //       (--mx-check; ntm/mx_gemm.hpp)                                    mx_check.cpp
 //   K8  per-XCD sweep that names a slow or wrong XCD, off by default
 //       (--xcd-sweep; ntm/xcd_sweep.hpp)                                 xcd_sweep.cpp
+//   K9  atomics and cross-XCD hand-off check: every kind of global atomic with a
+//       checked answer, plain stores handed between XCDs, off by default
+//       (env NTM_ATOMICS_CHECK=1; ntm/atomics.hpp)                       atomics.cpp
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)                                 collectives.hip
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL  collectives.hip
@@ -56,6 +59,12 @@ int main(int argc, char** argv) {
     if (const char* f = std::getenv("NTM_FAULT_INJECT")) o.fault = f;
   if ((o.fault == "slow_xcd" || o.fault == "corrupt_xcd") && !o.xcd_sweep) {
     std::fprintf(stderr, "fault-inject %s needs --xcd-sweep\n", o.fault.c_str());
+    usage();
+    return 2;
+  }
+  if (const char* a = std::getenv("NTM_ATOMICS_CHECK")) o.atomics_check = std::string(a) == "1";
+  if ((o.fault == "corrupt_atomic" || o.fault == "stale_handoff") && !o.atomics_check) {
+    std::fprintf(stderr, "fault-inject %s needs NTM_ATOMICS_CHECK=1\n", o.fault.c_str());
     usage();
     return 2;
   }

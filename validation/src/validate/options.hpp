@@ -37,6 +37,7 @@ struct Opts {
   double mx_tflops_floor = 0;   // 0 = report only
   bool xcd_sweep = false;       // K8: off unless asked for
   long xcd_sweep_mib = 256;     // MiB per XCD of the hbm level
+  bool atomics_check = false;   // K9: env NTM_ATOMICS_CHECK=1 (no flag yet: validate/README.md)
   double xcd_ratio = 0;         // fail an XCD below ratio x its card's median; 0 = report only
   long allreduce_max_mib = 8192;  // 8 GiB, capped by free HBM
   bool xgmi = true;

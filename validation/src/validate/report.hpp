@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "ntm/atomics_plan.hpp"
 #include "ntm/cu_sweep_plan.hpp"
 #include "ntm/host_link_plan.hpp"
 #include "ntm/xcd_sweep_plan.hpp"
@@ -227,6 +228,48 @@ struct XcdSweepResult {
   static void prometheus(std::ostream& p, const Gpus& res);
 };
 
+// K9: one op of the atomics check
+struct AtomicsOpRow {
+  int op = 0;
+  unsigned long long bad = 0;  // slots that differ from the reference table
+  double gops = 0;             // 1e9 atomic operations per second, reported only
+};
+
+// K9 (only with NTM_ATOMICS_CHECK=1)
+struct AtomicsResult {
+  bool ran = false;
+  std::vector<AtomicsOpRow> ops;
+  unsigned long long ticket_bad = 0, handoff_bad_words = 0, handoff_stale_words = 0;
+  double episodes_per_s = 0;
+  uint32_t xcds = 0, xcd_pairs_covered = 0;
+  std::vector<uint8_t> pairs;  // kMaxXcds x kMaxXcds, [writer][reader]
+  double seconds = 0;
+  std::vector<std::string> failures;  // empty = clean
+  std::string json() const {
+    if (!ran) return "";
+    std::string names = "[", per_op, m = "[";
+    for (size_t i = 0; i < ops.size(); ++i) {
+      const std::string n = ntm::atm::op_name(ops[i].op);
+      names += (i ? "," : "") + jstr(n);
+      per_op += ",\"atomics_" + n + "_bad\":" + std::to_string(ops[i].bad) + ",\"atomics_" + n + "_gops\":" +
+                jnum(ops[i].gops);
+    }
+    for (uint32_t w = 0; w < xcds && !pairs.empty(); ++w) {
+      m += w ? ",[" : "[";
+      for (uint32_t x = 0; x < xcds; ++x)
+        m += (x ? "," : "") + std::to_string((int)pairs[(size_t)w * ntm::atm::kMaxXcds + x]);
+      m += "]";
+    }
+    return ",\"atomics_ops\":" + names + "]" + per_op + ",\"atomics_ticket_bad\":" + std::to_string(ticket_bad) +
+           ",\"atomics_handoff_bad_words\":" + std::to_string(handoff_bad_words) +
+           ",\"atomics_handoff_stale_words\":" + std::to_string(handoff_stale_words) +
+           ",\"atomics_handoff_episodes_per_s\":" + jnum(episodes_per_s) +
+           ",\"atomics_xcd_pairs_covered\":" + std::to_string(xcd_pairs_covered) +
+           ",\"atomics_xcd_pairs\":" + m + "]" + ",\"atomics_seconds\":" + jnum(seconds);
+  }
+  static void prometheus(std::ostream& p, const Gpus& res);
+};
+
 struct GpuResult {
   int device = -1;
   std::string name, arch;
@@ -241,6 +284,7 @@ struct GpuResult {
   HostLinkResult host_link;
   MxResult mx;
   XcdSweepResult xcd;
+  AtomicsResult atomics;
 };
 
 // ------------------------------------------------------------ per-GPU verdicts
@@ -274,7 +318,7 @@ inline std::vector<std::string> gpu_failures(const GpuResult& r, const Opts& o) 
     out.push_back(d + "HBM " + jnum(r.total_gb) + " GB below " + jnum(o.min_hbm_gb) + " GB");
   if (!r.k2.copy_ok) out.push_back(d + "HBM copy mismatch");
   for (const auto* v : {&r.hbm_test.failures, &r.cu_sweep.failures, &r.host_link.failures, &r.mx.failures,
-                        &r.xcd.failures})
+                        &r.xcd.failures, &r.atomics.failures})
     out.insert(out.end(), v->begin(), v->end());
   if (o.hbm_floor_gbps > 0 && r.k2.copy_gbps < o.hbm_floor_gbps)
     out.push_back(d + "HBM copy " + jnum(r.k2.copy_gbps) + " GB/s below floor");
@@ -449,6 +493,35 @@ inline void XcdSweepResult::prometheus(std::ostream& p, const Gpus& res) {
   }
 }
 
+// the rate per op carries an op label, so no gauge() for it
+inline void AtomicsResult::prometheus(std::ostream& p, const Gpus& res) {
+  auto ran = [](const GpuResult& r) { return r.atomics.ran; };
+  gauge(p, res, "amdgpu_validate_atomics_bad_slots", "Table slots of the atomics check that differ from the reference.",
+        ran, [](const GpuResult& r) {
+          unsigned long long n = 0;
+          for (auto& o : r.atomics.ops) n += o.bad;
+          return n;
+        });
+  p << "# HELP amdgpu_validate_atomics_gops Atomic operations per second of one op, in 1e9.\n"
+    << "# TYPE amdgpu_validate_atomics_gops gauge\n";
+  for (auto& r : res)
+    for (auto& o : r.atomics.ops)
+      p << "amdgpu_validate_atomics_gops{gpu=\"" << r.device << "\",op=\"" << ntm::atm::op_name(o.op) << "\"} "
+        << jnum(o.gops) << "\n";
+  gauge(p, res, "amdgpu_validate_atomics_ticket_bad", "Tickets missing, duplicate or invalid, and counters off.", ran,
+        [](const GpuResult& r) { return r.atomics.ticket_bad; });
+  gauge(p, res, "amdgpu_validate_atomics_handoff_bad_words", "16-byte words a hand-off's reader found wrong.", ran,
+        [](const GpuResult& r) { return r.atomics.handoff_bad_words; });
+  gauge(p, res, "amdgpu_validate_atomics_handoff_stale_words", "Of them, words that held last round's pattern.", ran,
+        [](const GpuResult& r) { return r.atomics.handoff_stale_words; });
+  gauge(p, res, "amdgpu_validate_atomics_handoff_episodes_per_s", "Hand-off episodes per second.", ran,
+        [](const GpuResult& r) { return jnum(r.atomics.episodes_per_s); });
+  gauge(p, res, "amdgpu_validate_atomics_xcd_pairs_covered", "Ordered writer -> reader XCD pairs a hand-off checked.", ran,
+        [](const GpuResult& r) { return r.atomics.xcd_pairs_covered; });
+  gauge(p, res, "amdgpu_validate_atomics_seconds", "Seconds the atomics check took.", ran,
+        [](const GpuResult& r) { return jnum(r.atomics.seconds); });
+}
+
 // node-exporter textfile-collector format (--prom-out) and Pushgateway body
 // (--pushgateway); labels carry the device index.
 inline std::string prometheus_text(const Report& R) {
@@ -474,6 +547,7 @@ inline std::string prometheus_text(const Report& R) {
   if (o.host_link_mib > 0) HostLinkResult::prometheus(p, R.gpus);
   if (o.xcd_sweep) XcdSweepResult::prometheus(p, R.gpus);
   if (o.mx_check) MxResult::prometheus(p, R.gpus);
+  if (o.atomics_check) AtomicsResult::prometheus(p, R.gpus);
   if (!R.rccl_rows.empty() || !R.xgmi_rows.empty())
     p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
       << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(Report::peak_any(R.rccl_rows)) << "\n"
@@ -504,7 +578,7 @@ inline std::string report_json(const Report& R) {
     js += (i ? "," : "") + std::string("{\"device\":") + std::to_string(r.device) +
           ",\"name\":" + jstr(r.name) + ",\"arch\":" + jstr(r.arch) + ",\"hbm_total_gb\":" + jnum(r.total_gb) +
           r.k1.json() + r.fp8.json() + r.sk.json() + r.k2.json() + r.hbm_test.json() + r.cu_sweep.json() +
-          r.host_link.json() + r.mx.json() + r.xcd.json() + "}";
+          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(R.rccl_rows);
   js += ",\"xgmi_allreduce_bf16\":" + coll_json(R.xgmi_rows);
