@@ -369,6 +369,12 @@ variable "validation_atomics_check" {
   description = "Run the Job's atomics and cross-XCD hand-off check (K9): every kind of global atomic (integer add / and / or / xor / min / max, compare-and-swap, fp32 / fp64 / packed bf16 / packed fp16 add) on a table whose exact answer a kernel without atomics computes, a ticket draw in which every ticket must be handed out exactly once, and plain stores handed from one XCD to another under agent-scope release / acquire with every word compared. A wrong slot, a lost ticket or a stale word fails the Job by op and slot, head and ticket, or reader and writer XCD; rates are reported. It sets NTM_ATOMICS_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/atomics/README.md."
 }
 
+variable "validation_mcore_check" {
+  type        = bool
+  default     = false
+  description = "Run the Job's matrix-core check of the formats K1 and K7 never issue (K10): the fp64, fp32, fp16 and int8 MFMAs and the 2:4 structured-sparse bf16 and int8 SMFMACs, each with a decode sweep (one non-zero per dot product) and a dense product whose operands keep every partial sum an exact integer, compared bitwise with a reference kernel that uses no matrix instruction, then a verified 4096^3 fp64 and int8 product whose rates are reported. A wrong element fails the Job by format, row and column. It sets NTM_MCORE_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/mcore/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

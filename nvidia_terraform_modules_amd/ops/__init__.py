@@ -23,6 +23,10 @@ K8 ``xcd_sweep_read``, ``xcd_sweep_mfma``, ``xcd_sweep_summarize`` - a verified 
 K9 ``atomics_rmw``, ``atomics_rmw_reference``, ``atomics_tickets``, ``atomics_handoff``,
    ``atomics_summarize`` - every kind of global atomic with a checked answer, and plain stores
    handed from one XCD to another under agent-scope release / acquire.
+K10 ``mcore_gemm``, ``mcore_reference_gpu``, ``mcore_compare`` - the fp64, fp32, fp16 and int8
+   MFMAs and the 2:4-sparse bf16 / int8 SMFMACs with exact answers, a reference without
+   matrix instructions and a bitwise compare; ``mcore_make_inputs``, ``mcore_matmul_bits``,
+   ``mcore_exact``, ``mcore_compress``, ``mcore_expand`` - the host side (numpy, ``ops.mcore``).
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -104,7 +108,24 @@ from .kernels import (  # noqa: F401
     atomics_rmw_reference,
     atomics_summarize,
     atomics_tickets,
+    McoreCompareReport,
+    mcore_compare,
+    mcore_gemm,
+    mcore_reference_gpu,
+    mcore_to_device,
     verify_bf16,
+)
+from .mcore import (  # noqa: F401
+    MCORE_FORMATS,
+    mcore_compress,
+    mcore_decode_windows,
+    mcore_exact,
+    mcore_expand,
+    mcore_failure_message,
+    mcore_format,
+    mcore_make_inputs,
+    mcore_matmul_bits,
+    mcore_max_abits,
 )
 from .mx import (  # noqa: F401
     MX_FORMATS,

@@ -165,6 +165,10 @@ SIGNATURES = {
     "ntm_atomics_summarize_rmw": ([c_int, c_vp, c_vp, c_u64, c_int, c_vp, c_size], c_size),
     "ntm_atomics_summarize_tickets": ([c_vp, c_vp, c_uint, c_uint, c_uint, c_int, c_vp, c_size], c_size),
     "ntm_atomics_summarize_handoff": ([c_vp, c_size, c_uint, c_uint, c_uint, c_uint, c_int, c_vp, c_size], c_size),
+    "ntm_mcore_gemm": ([c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_mcore_reference": ([c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_mcore_compare": ([c_vp, c_vp, c_size, c_int, c_vp, c_vp], c_int),
+    "ntm_mcore_mismatch_bytes": ([], c_int),
 }
 
 XGMI_SIGNATURES = {
@@ -220,6 +224,7 @@ def _declare_experimental(lib: ctypes.CDLL) -> None:
             [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp], c_int),
         "ntm_mfma_f8_probe": ([c_vp, c_vp, c_vp, c_vp], c_int),
         "ntm_mx_mfma_probe": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp], c_int),
+        "ntm_mcore_mfma_probe": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp], c_int),
         "ntm_mfma_rate": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_mfma_toggle": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_dma_probe": ([c_int, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),

@@ -328,3 +328,52 @@ def mx_compare(expected: torch.Tensor, got: torch.Tensor) -> MxCompareReport:
     if not idx.size:
         return MxCompareReport(0, None, None, None)
     return MxCompareReport(int(idx.size), int(idx[0]), int(e[idx[0]]), int(g[idx[0]]))
+
+
+
+# K10 on the CPU: every product is the exact numpy reference (ops/mcore.py)
+from . import mcore as _mcore  # noqa: E402
+from .kernels import McoreCompareReport, mcore_check_args  # noqa: E402
+from .mcore import (MCORE_FORMATS, mcore_compress, mcore_decode_windows, mcore_exact,  # noqa: E402,F401
+                    mcore_expand, mcore_failure_message, mcore_make_inputs, mcore_matmul_bits,
+                    mcore_max_abits)
+
+
+def mcore_to_device(inputs: dict, device) -> dict:
+    def t(x):
+        if x is None:
+            return None
+        if x.dtype == np.uint16:
+            return torch.from_numpy(x.view(np.int16).copy()).view(torch.bfloat16)
+        return torch.from_numpy(x.copy())
+    return {**inputs, "a": t(inputs["a"]), "ai": t(inputs["ai"]), "b": t(inputs["b"])}
+
+
+def mcore_gemm(a, b, fmt, ai=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    mcore_check_args(a, b, fmt, ai, out, need_cuda=False)
+    f = _mcore.mcore_format(fmt)
+
+    def arr(t):
+        return t.view(torch.int16).numpy().view(np.uint16) if t.dtype == torch.bfloat16 else t.numpy()
+    bits = _mcore.mcore_matmul_bits(arr(a), arr(b), fmt, None if ai is None else ai.numpy())
+    acc = np.int32 if f["integer"] else np.float64 if f["acc_bytes"] == 8 else np.float32
+    c = torch.from_numpy(bits.view(acc).copy())
+    if out is None:
+        return c
+    out.copy_(c)
+    return out
+
+
+mcore_reference_gpu = mcore_gemm
+
+
+def mcore_compare(expected: torch.Tensor, got: torch.Tensor) -> McoreCompareReport:
+    word = np.uint64 if expected.element_size() == 8 else np.uint32
+    e = _bytes_of(expected).view(word)
+    g = _bytes_of(got).view(word)
+    if e.size != g.size:
+        raise ValueError("mcore_compare needs two tensors of one size")
+    idx = np.flatnonzero(e != g)
+    if not idx.size:
+        return McoreCompareReport(0, None, None, None)
+    return McoreCompareReport(int(idx.size), int(idx[0]), int(e[idx[0]]), int(g[idx[0]]))

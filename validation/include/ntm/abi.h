@@ -159,6 +159,12 @@ NTM_API size_t ntm_atomics_summarize_rmw(int op, const void* got, const void* ex
 NTM_API size_t ntm_atomics_summarize_tickets(const void* counters, const void* claim, unsigned heads, unsigned grid, unsigned iters, int gpu, char* json, size_t cap);
 NTM_API size_t ntm_atomics_summarize_handoff(const void* records, size_t n, unsigned episodes, unsigned episode_size, unsigned xcds, unsigned launches, int gpu, char* json, size_t cap);
 
+/* ---- K10 fp64 / fp32 / fp16 / int8 / 2:4-sparse matrix-core check (ntm/mcore.hpp, ntm/mcore_plan.hpp) */
+NTM_API int ntm_mcore_gemm(int fmt, const void* A, const void* AI, const void* B, void* C, int M, int N, int K, void* stream);
+NTM_API int ntm_mcore_reference(int fmt, const void* A, const void* AI, const void* B, void* C, int M, int N, int K, void* stream);
+NTM_API int ntm_mcore_compare(const void* expected, const void* got, size_t n, int word_bytes, void* out, void* stream);
+NTM_API int ntm_mcore_mismatch_bytes(void);
+
 /* ---- C2 hand-written xGMI all-reduce (xgmi_allreduce.hip, ntm/xgmi_allreduce.hpp)
  * and the allocation / HIP IPC helpers its Python side needs */
 NTM_API int ntm_xgmi_allreduce_bf16(const void* const* in_ptrs, void* const* out_ptrs, unsigned* const* sig_ptrs, int nranks, int rank_base, int nranks_here, int nblk, size_t count, unsigned epoch, unsigned* err, int one_shot, void* stream);

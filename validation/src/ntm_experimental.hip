@@ -33,6 +33,7 @@
 #include "ntm/gemm_w4k.hpp"
 #include "ntm/gemm_bf16_t128.hpp"
 #include "ntm/gemm_fp8_diag.hpp"
+#include "ntm/mcore.hpp"
 #include "ntm/mx_gemm.hpp"
 #include "ntm/stream_policy_exp.hpp"
 
@@ -286,6 +287,60 @@ NTM_API int ntm_mx_mfma_probe(int fmt, const void* a_stage, const void* b_stage,
     case 2: hipLaunchKernelGGL(mx_mfma_probe_kernel<2>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
     case 3: hipLaunchKernelGGL(mx_mfma_probe_kernel<3>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
     case 4: hipLaunchKernelGGL(mx_mfma_probe_kernel<4>, dim3(1), dim3(64), 0, S(stream), a, b, x, y, o); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
+
+// K10 lane-map probe: one matrix instruction of format fmt (ntm/mcore_plan.hpp) on
+// caller-built register images, no LDS and no tile logic in between. a_stage 64 lanes x
+// 16 B (f64 / f32 use the first 8 / 4), b_stage 64 x 32 B (the dense formats use the first
+// 8 / 4 / 16 / 16), idx 64 index VGPRs (sparse formats only), d 64 x 32 B: four results per
+// lane in register order, 8 bytes apart for f64 and 4 bytes apart otherwise. cbsz 0 .. 1
+// and abid 0 .. 3 go into the sparse instructions' immediates and are 0 for the dense ones.
+namespace {
+template <int FMT, int CBSZ, int ABID>
+__global__ void __launch_bounds__(64) mcore_mfma_probe_kernel(const unsigned char* a, const unsigned char* b,
+                                                              const int* idx, unsigned char* d) {
+  namespace mc = ntm::mc;
+  const int l = threadIdx.x;
+  const unsigned char *pa = a + l * 16, *pb = b + l * 32;
+  typename mc::Tile<FMT>::Acc c = {0, 0, 0, 0};
+  if constexpr (FMT == mc::kSpBf16)
+    c = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(*(const ntm::bf16x8*)pa, *(const mc::bf16x16*)pb, c, idx[l], CBSZ, ABID);
+  else if constexpr (FMT == mc::kSpI8)
+    c = __builtin_amdgcn_smfmac_i32_16x16x128_i8(*(const mc::i32x4*)pa, *(const mc::i32x8*)pb, c, idx[l], CBSZ, ABID);
+  else  // the GEMM's own wrapper with lane group 0's offsets: the fragment starts at the pointer
+    c = mc::mma<FMT>(pa, nullptr, pb, 0, 0, c);
+  *(typename mc::Tile<FMT>::Acc*)(d + l * 32) = c;
+}
+template <int FMT>
+hipError_t mcore_probe_imm(int cbsz, int abid, const unsigned char* a, const unsigned char* b, const int* idx,
+                           unsigned char* d, hipStream_t s) {
+#define NTM_MCP(C, A) \
+  if (cbsz == C && abid == A) hipLaunchKernelGGL((mcore_mfma_probe_kernel<FMT, C, A>), dim3(1), dim3(64), 0, s, a, b, idx, d);
+  NTM_MCP(0, 0) NTM_MCP(0, 1) NTM_MCP(0, 2) NTM_MCP(0, 3) NTM_MCP(1, 0) NTM_MCP(1, 1) NTM_MCP(1, 2) NTM_MCP(1, 3)
+#undef NTM_MCP
+  return hipGetLastError();
+}
+}  // namespace
+
+NTM_API int ntm_mcore_mfma_probe(int fmt, const void* a_stage, const void* b_stage, const void* idx, int cbsz,
+                                 int abid, void* d, void* stream) {
+  namespace mc = ntm::mc;
+  auto* a = (const unsigned char*)a_stage;
+  auto* b = (const unsigned char*)b_stage;
+  auto* x = (const int*)idx;
+  auto* o = (unsigned char*)d;
+  if (!a || !b || !x || !o || cbsz < 0 || cbsz > 1 || abid < 0 || abid > 3) return (int)hipErrorInvalidValue;
+  if (fmt < mc::kSpBf16 && (cbsz || abid)) return (int)hipErrorInvalidValue;
+  switch (fmt) {
+    case mc::kF64: hipLaunchKernelGGL((mcore_mfma_probe_kernel<mc::kF64, 0, 0>), dim3(1), dim3(64), 0, S(stream), a, b, x, o); break;
+    case mc::kF32: hipLaunchKernelGGL((mcore_mfma_probe_kernel<mc::kF32, 0, 0>), dim3(1), dim3(64), 0, S(stream), a, b, x, o); break;
+    case mc::kF16: hipLaunchKernelGGL((mcore_mfma_probe_kernel<mc::kF16, 0, 0>), dim3(1), dim3(64), 0, S(stream), a, b, x, o); break;
+    case mc::kI8: hipLaunchKernelGGL((mcore_mfma_probe_kernel<mc::kI8, 0, 0>), dim3(1), dim3(64), 0, S(stream), a, b, x, o); break;
+    case mc::kSpBf16: return (int)mcore_probe_imm<mc::kSpBf16>(cbsz, abid, a, b, x, o, S(stream));
+    case mc::kSpI8: return (int)mcore_probe_imm<mc::kSpI8>(cbsz, abid, a, b, x, o, S(stream));
     default: return (int)hipErrorInvalidValue;
   }
   return (int)hipGetLastError();

@@ -1,7 +1,8 @@
 // C ABI over the MI355X validation kernels (K1 GEMM, K2 HBM stream,
 // K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep,
 // K6 host-link check, K7 MX block-scaled matrix check, K8 per-XCD sweep,
-// K9 atomics and cross-XCD hand-off check).
+// K9 atomics and cross-XCD hand-off check, K10 fp64 / fp32 / fp16 / int8 / sparse
+// matrix-core check).
 // Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
@@ -27,6 +28,7 @@
 #include "ntm/gemm_w4k.hpp"
 #include "ntm/hbm_pattern.hpp"
 #include "ntm/host_link.hpp"
+#include "ntm/mcore.hpp"
 #include "ntm/mx_gemm.hpp"
 #include "ntm/xcd_sweep.hpp"
 
@@ -1155,3 +1157,23 @@ NTM_API size_t ntm_atomics_summarize_handoff(const void* records, size_t n, unsi
   return put_json(atm::handoff_json(atm::summarize_handoff(recs.data(), n, episodes, episode_size, xcds, launches, gpu)),
                   json, cap);
 }
+
+// K10: matrix-core check of the formats K1 and K7 never issue (mcore.hpp; formats,
+// generators, bound and messages in mcore_plan.hpp). fmt: 0 f64, 1 f32, 2 f16, 3 i8,
+// 4 sp_bf16, 5 sp_i8. A is [M][K] elements, or for a sparse format Ac [M][K/2] with AI
+// [M][K/4] index bytes (ignored otherwise); B is [N][K]; C is [M][N] fp64 / fp32 / int32.
+// A bad format, shape or pointer returns hipErrorInvalidValue and launches nothing.
+NTM_API int ntm_mcore_gemm(int fmt, const void* A, const void* AI, const void* B, void* C, int M, int N, int K,
+                           void* stream) {
+  return (int)ntm::mc::launch_mcore(false, fmt, A, AI, B, C, M, N, K, S(stream));
+}
+NTM_API int ntm_mcore_reference(int fmt, const void* A, const void* AI, const void* B, void* C, int M, int N, int K,
+                                void* stream) {
+  return (int)ntm::mc::launch_mcore(true, fmt, A, AI, B, C, M, N, K, S(stream));
+}
+// `out`: ntm_mcore_mismatch_bytes() of device memory holding {0, ~0, 0, 0} as 64-bit words.
+NTM_API int ntm_mcore_compare(const void* expected, const void* got, size_t n, int word_bytes, void* out,
+                              void* stream) {
+  return (int)ntm::mc::launch_mcore_compare(expected, got, n, word_bytes, out, S(stream));
+}
+NTM_API int ntm_mcore_mismatch_bytes() { return (int)sizeof(ntm::mc::Mismatch); }

@@ -21,6 +21,9 @@
 //   K9  atomics and cross-XCD hand-off check: every kind of global atomic with a
 //       checked answer, plain stores handed between XCDs, off by default
 //       (env NTM_ATOMICS_CHECK=1; ntm/atomics.hpp)                       atomics.cpp
+//   K10 fp64 / fp32 / fp16 / int8 / 2:4-sparse matrix-core check: every matrix
+//       instruction K1 and K7 never issue, exact answers, off by default
+//       (env NTM_MCORE_CHECK=1; ntm/mcore.hpp)                           mcore.cpp
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)                                 collectives.hip
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL  collectives.hip
@@ -65,6 +68,12 @@ int main(int argc, char** argv) {
   if (const char* a = std::getenv("NTM_ATOMICS_CHECK")) o.atomics_check = std::string(a) == "1";
   if ((o.fault == "corrupt_atomic" || o.fault == "stale_handoff") && !o.atomics_check) {
     std::fprintf(stderr, "fault-inject %s needs NTM_ATOMICS_CHECK=1\n", o.fault.c_str());
+    usage();
+    return 2;
+  }
+  if (const char* a = std::getenv("NTM_MCORE_CHECK")) o.mcore_check = std::string(a) == "1";
+  if (o.fault == "corrupt_mcore" && !o.mcore_check) {
+    std::fprintf(stderr, "fault-inject corrupt_mcore needs NTM_MCORE_CHECK=1\n");
     usage();
     return 2;
   }

@@ -21,6 +21,7 @@
 #include "ntm/atomics_plan.hpp"
 #include "ntm/cu_sweep_plan.hpp"
 #include "ntm/host_link_plan.hpp"
+#include "ntm/mcore_plan.hpp"
 #include "ntm/xcd_sweep_plan.hpp"
 
 #include "json.hpp"
@@ -270,6 +271,28 @@ struct AtomicsResult {
   static void prometheus(std::ostream& p, const Gpus& res);
 };
 
+// K10 (only with NTM_MCORE_CHECK=1)
+struct McoreResult {
+  bool ran = false;
+  unsigned long long bad[ntm::mc::kFormats] = {};  // result words that differ, decode sweep and dense runs
+  double f64_tflops = 0, i8_tops = 0;              // the verified 4096^3 products, reported only
+  double seconds = 0;
+  std::vector<std::string> failures;  // empty = clean
+  double rate(int fmt) const { return fmt == ntm::mc::kF64 ? f64_tflops : i8_tops; }
+  std::string json() const {
+    if (!ran) return "";
+    std::string names = "[", per;
+    for (int f = 0; f < ntm::mc::kFormats; ++f) {
+      const std::string n = ntm::mc::format_name(f);
+      names += (f ? "," : "") + jstr(n);
+      per += ",\"mcore_" + n + "_bad\":" + std::to_string(bad[f]);
+    }
+    return ",\"mcore_formats\":" + names + "]" + per + ",\"mcore_f64_tflops\":" + jnum(f64_tflops) +
+           ",\"mcore_i8_tops\":" + jnum(i8_tops) + ",\"mcore_seconds\":" + jnum(seconds);
+  }
+  static void prometheus(std::ostream& p, const Gpus& res);
+};
+
 struct GpuResult {
   int device = -1;
   std::string name, arch;
@@ -285,6 +308,7 @@ struct GpuResult {
   MxResult mx;
   XcdSweepResult xcd;
   AtomicsResult atomics;
+  McoreResult mcore;
 };
 
 // ------------------------------------------------------------ per-GPU verdicts
@@ -318,7 +342,7 @@ inline std::vector<std::string> gpu_failures(const GpuResult& r, const Opts& o) 
     out.push_back(d + "HBM " + jnum(r.total_gb) + " GB below " + jnum(o.min_hbm_gb) + " GB");
   if (!r.k2.copy_ok) out.push_back(d + "HBM copy mismatch");
   for (const auto* v : {&r.hbm_test.failures, &r.cu_sweep.failures, &r.host_link.failures, &r.mx.failures,
-                        &r.xcd.failures, &r.atomics.failures})
+                        &r.xcd.failures, &r.atomics.failures, &r.mcore.failures})
     out.insert(out.end(), v->begin(), v->end());
   if (o.hbm_floor_gbps > 0 && r.k2.copy_gbps < o.hbm_floor_gbps)
     out.push_back(d + "HBM copy " + jnum(r.k2.copy_gbps) + " GB/s below floor");
@@ -522,6 +546,23 @@ inline void AtomicsResult::prometheus(std::ostream& p, const Gpus& res) {
         [](const GpuResult& r) { return jnum(r.atomics.seconds); });
 }
 
+// both gauges carry a format label, so no gauge() for them
+inline void McoreResult::prometheus(std::ostream& p, const Gpus& res) {
+  p << "# HELP amdgpu_validate_mcore_bad Result words of the matrix-core check that differ from the exact answer.\n"
+    << "# TYPE amdgpu_validate_mcore_bad gauge\n";
+  for (auto& r : res)
+    for (int f = 0; r.mcore.ran && f < ntm::mc::kFormats; ++f)
+      p << "amdgpu_validate_mcore_bad{gpu=\"" << r.device << "\",format=\"" << ntm::mc::format_name(f) << "\"} "
+        << r.mcore.bad[f] << "\n";
+  p << "# HELP amdgpu_validate_mcore_rate Verified 4096^3 product, 1e12 operations per second (reported only).\n"
+    << "# TYPE amdgpu_validate_mcore_rate gauge\n";
+  for (auto& r : res)
+    for (int f : {ntm::mc::kF64, ntm::mc::kI8})
+      if (r.mcore.ran)
+        p << "amdgpu_validate_mcore_rate{gpu=\"" << r.device << "\",format=\"" << ntm::mc::format_name(f) << "\"} "
+          << jnum(r.mcore.rate(f)) << "\n";
+}
+
 // node-exporter textfile-collector format (--prom-out) and Pushgateway body
 // (--pushgateway); labels carry the device index.
 inline std::string prometheus_text(const Report& R) {
@@ -548,6 +589,7 @@ inline std::string prometheus_text(const Report& R) {
   if (o.xcd_sweep) XcdSweepResult::prometheus(p, R.gpus);
   if (o.mx_check) MxResult::prometheus(p, R.gpus);
   if (o.atomics_check) AtomicsResult::prometheus(p, R.gpus);
+  if (o.mcore_check) McoreResult::prometheus(p, R.gpus);
   if (!R.rccl_rows.empty() || !R.xgmi_rows.empty())
     p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
       << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(Report::peak_any(R.rccl_rows)) << "\n"
@@ -578,7 +620,7 @@ inline std::string report_json(const Report& R) {
     js += (i ? "," : "") + std::string("{\"device\":") + std::to_string(r.device) +
           ",\"name\":" + jstr(r.name) + ",\"arch\":" + jstr(r.arch) + ",\"hbm_total_gb\":" + jnum(r.total_gb) +
           r.k1.json() + r.fp8.json() + r.sk.json() + r.k2.json() + r.hbm_test.json() + r.cu_sweep.json() +
-          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + "}";
+          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(R.rccl_rows);
   js += ",\"xgmi_allreduce_bf16\":" + coll_json(R.xgmi_rows);
