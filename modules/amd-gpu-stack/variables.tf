@@ -375,6 +375,12 @@ variable "validation_mcore_check" {
   description = "Run the Job's matrix-core check of the formats K1 and K7 never issue (K10): the fp64, fp32, fp16 and int8 MFMAs and the 2:4 structured-sparse bf16 and int8 SMFMACs, each with a decode sweep (one non-zero per dot product) and a dense product whose operands keep every partial sum an exact integer, compared bitwise with a reference kernel that uses no matrix instruction, then a verified 4096^3 fp64 and int8 product whose rates are reported. A wrong element fails the Job by format, row and column. It sets NTM_MCORE_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/mcore/README.md."
 }
 
+variable "validation_mxq_check" {
+  type        = bool
+  default     = false
+  description = "Run the Job's device-side MX quantise / dequantise check (K11): the gfx950 scaled-conversion instructions quantise fp32 and bf16 to e4m3, e5m2, e2m3, e3m2 and e2m1 with an E8M0 scale per 32 elements (OCP MX v1.0) and back, compared bitwise with reference kernels that use integer arithmetic only - conversion sweeps over every rounding boundary, every finite bf16 code and every code at every scale byte, a block quantise of a 1024 x 4096 matrix, and an end-to-end product of operands quantised on the device through the K7 GEMM; the quantise rate is reported. A wrong word fails the Job by format, sub-test, row and element. It sets NTM_MXQ_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/mxq/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

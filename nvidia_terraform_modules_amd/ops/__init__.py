@@ -27,6 +27,11 @@ K10 ``mcore_gemm``, ``mcore_reference_gpu``, ``mcore_compare`` - the fp64, fp32,
    MFMAs and the 2:4-sparse bf16 / int8 SMFMACs with exact answers, a reference without
    matrix instructions and a bitwise compare; ``mcore_make_inputs``, ``mcore_matmul_bits``,
    ``mcore_exact``, ``mcore_compress``, ``mcore_expand`` - the host side (numpy, ``ops.mcore``).
+K11 ``mx_quantize``, ``mx_dequantize``, ``mxq_cvt`` - MX quantise / dequantise on the device with
+   the scaled-conversion instructions, producing what ``mx_gemm`` takes;
+   ``mx_quantize_reference_gpu``, ``mx_dequantize_reference_gpu`` - the same by integer
+   arithmetic; ``mxq_quantize_bits``, ``mxq_dequantize_bits``, ``mxq_make_inputs`` - the host
+   side (numpy, ``ops.mxq``).
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -113,7 +118,25 @@ from .kernels import (  # noqa: F401
     mcore_gemm,
     mcore_reference_gpu,
     mcore_to_device,
+    mx_dequantize,
+    mx_dequantize_reference_gpu,
+    mx_quantize,
+    mx_quantize_reference_gpu,
+    mxq_cvt,
+    mxq_to_device,
     verify_bf16,
+)
+from .mxq import (  # noqa: F401
+    MXQ_EMAX,
+    MXQ_MAX_CODE,
+    mx_bits,
+    mxq_dequantize_bits,
+    mxq_failure_message,
+    mxq_make_inputs,
+    mxq_quantize_bits,
+    mxq_quantize_codes,
+    mxq_scale_bytes,
+    mxq_shape_ok,
 )
 from .mcore import (  # noqa: F401
     MCORE_FORMATS,

@@ -169,6 +169,13 @@ SIGNATURES = {
     "ntm_mcore_reference": ([c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
     "ntm_mcore_compare": ([c_vp, c_vp, c_size, c_int, c_vp, c_vp], c_int),
     "ntm_mcore_mismatch_bytes": ([], c_int),
+    "ntm_mxq_shape_ok": ([c_int, c_int, c_int], c_int),
+    "ntm_mxq_quantize": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_u64, c_vp], c_int),
+    "ntm_mxq_dequantize": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_mxq_cvt": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_u64, c_vp], c_int),
+    "ntm_mxq_reference_quantize": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_mxq_reference_dequantize": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_mxq_reference_cvt": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
 }
 
 XGMI_SIGNATURES = {
@@ -225,6 +232,7 @@ def _declare_experimental(lib: ctypes.CDLL) -> None:
         "ntm_mfma_f8_probe": ([c_vp, c_vp, c_vp, c_vp], c_int),
         "ntm_mx_mfma_probe": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp], c_int),
         "ntm_mcore_mfma_probe": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp], c_int),
+        "ntm_mxq_cvt_probe": ([c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp], c_int),
         "ntm_mfma_rate": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_mfma_toggle": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_dma_probe": ([c_int, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),

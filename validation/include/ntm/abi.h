@@ -165,6 +165,15 @@ NTM_API int ntm_mcore_reference(int fmt, const void* A, const void* AI, const vo
 NTM_API int ntm_mcore_compare(const void* expected, const void* got, size_t n, int word_bytes, void* out, void* stream);
 NTM_API int ntm_mcore_mismatch_bytes(void);
 
+/* ---- K11 MX quantise / dequantise on the device (ntm/mxq.hpp, ntm/mxq_plan.hpp) */
+NTM_API int ntm_mxq_shape_ok(int R, int K, int ldx);
+NTM_API int ntm_mxq_quantize(int fmt, int src_dtype, const void* x, void* packed, void* scales, int R, int K, int ldx, int rounding, unsigned long long seed, void* stream);
+NTM_API int ntm_mxq_dequantize(int fmt, int dst_dtype, const void* packed, const void* scales, void* y, int R, int K, int ldx, void* stream);
+NTM_API int ntm_mxq_cvt(int fmt, int src_dtype, const void* x, const void* scales, void* packed, int R, int K, int ldx, int rounding, unsigned long long seed, void* stream);
+NTM_API int ntm_mxq_reference_quantize(int fmt, int src_dtype, const void* x, void* packed, void* scales, int R, int K, int ldx, void* stream);
+NTM_API int ntm_mxq_reference_dequantize(int fmt, int dst_dtype, const void* packed, const void* scales, void* y, int R, int K, int ldx, void* stream);
+NTM_API int ntm_mxq_reference_cvt(int fmt, int src_dtype, const void* x, const void* scales, void* packed, int R, int K, int ldx, void* stream);
+
 /* ---- C2 hand-written xGMI all-reduce (xgmi_allreduce.hip, ntm/xgmi_allreduce.hpp)
  * and the allocation / HIP IPC helpers its Python side needs */
 NTM_API int ntm_xgmi_allreduce_bf16(const void* const* in_ptrs, void* const* out_ptrs, unsigned* const* sig_ptrs, int nranks, int rank_base, int nranks_here, int nblk, size_t count, unsigned epoch, unsigned* err, int one_shot, void* stream);

@@ -16,6 +16,13 @@
 #include <string>
 #include <vector>
 
+// hash32 also runs in the K11 kernels (ntm/mxq.hpp)
+#if defined(__HIPCC__)
+#define NTM_MX_HD __host__ __device__
+#else
+#define NTM_MX_HD
+#endif
+
 namespace ntm {
 namespace mx {
 
@@ -137,7 +144,7 @@ inline int unpack_code(int fmt, const uint8_t* row, int k) {
 
 // ---- the generators: K4's counter hash (hbm_pattern.hpp HASH) of a word
 // index, one stream per array.
-inline uint32_t hash32(uint64_t seed, uint32_t stream, uint64_t idx) {
+NTM_MX_HD inline uint32_t hash32(uint64_t seed, uint32_t stream, uint64_t idx) {
   const uint64_t w = ((uint64_t)stream << 32) + idx;
   const uint64_t s = seed + (uint64_t)stream * 0x9E3779B97F4A7C15ull;
   uint32_t x = (uint32_t)w + (uint32_t)s;

@@ -35,6 +35,7 @@
 #include "ntm/gemm_fp8_diag.hpp"
 #include "ntm/mcore.hpp"
 #include "ntm/mx_gemm.hpp"
+#include "ntm/mxq.hpp"
 #include "ntm/stream_policy_exp.hpp"
 
 #include "ntm/abi.h"  // NTM_API; this file's own exports are for tests only and are declared here
@@ -370,4 +371,81 @@ NTM_API int ntm_dma_probe(int mode, const void* base, int pitch, int T, int reps
                           void* stream) {
   return (int)ntm::dprobe::launch_dma_probe(mode, (const __bf16*)base, pitch, T, reps, grid,
                                             S(stream));
+}
+
+// K11 conversion probe: one scaled-conversion instruction per lane on caller-built operands
+// (tools/mxq_cvt_probe.py). Lane l reads 32 floats src[32 l ..] (the down forms use the first
+// 2, or all 32 as two vectors of 16; the up forms read dwords 0 .. 5 as the packed source),
+// the scale operand's bits scale[l], the random word rnd[l] and the destination's old value
+// old[l]; it writes 32 dwords out[32 l ..]. sel 0 .. 3 is the byte / half selector immediate.
+// op: 0 pk_fp4_f32, 1 pk_fp4_bf16 (the two bf16 halves of src dword 0), 2 pk_fp8_f32,
+// 3 pk_bf8_f32, 4 2xpk16_fp6_f32, 5 2xpk16_bf6_f32, 6 pk_f32_fp4, 7 pk_f32_fp8, 8 pk_f32_bf8,
+// 9 pk32_f32_fp6, 10 pk32_f32_bf6, 11 sr_pk_fp4_f32, 12 sr_fp8_f32.
+namespace {
+template <int OP, int SEL>
+__global__ void __launch_bounds__(64) mxq_cvt_probe_kernel(const float* src, const unsigned* scale,
+                                                           const unsigned* rnd, const unsigned* old, unsigned* out,
+                                                           int n) {
+  namespace q = ntm::mxq;
+  namespace mx = ntm::mx;
+  const int l = blockIdx.x * 64 + threadIdx.x;
+  if (l >= n) return;
+  const float* a = src + (size_t)l * 32;
+  const unsigned* au = (const unsigned*)a;
+  unsigned* o = out + (size_t)l * 32;
+  const float sc = q::as_f(scale[l]);
+  if constexpr (OP == 0) o[0] = q::cvt_pk_down<mx::kFmtE2M1, SEL>(old[l], a[0], a[1], sc);
+  if constexpr (OP == 1)
+    o[0] = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(old[l], __builtin_bit_cast(q::bf16x2, au[0]), sc, SEL);
+  if constexpr (OP == 2) o[0] = q::cvt_pk_down<mx::kFmtE4M3, SEL & 1>(old[l], a[0], a[1], sc);
+  if constexpr (OP == 3) o[0] = q::cvt_pk_down<mx::kFmtE5M2, SEL & 1>(old[l], a[0], a[1], sc);
+  if constexpr (OP == 4 || OP == 5) {
+    const q::f32x16 x = *(const q::f32x16*)a, y = *(const q::f32x16*)(a + 16);
+    const q::u32x6 r = q::cvt_pk32_down<OP == 4 ? mx::kFmtE2M3 : mx::kFmtE3M2>(x, y, sc);
+    for (int i = 0; i < 6; ++i) o[i] = r[i];
+  }
+  if constexpr (OP >= 6 && OP <= 8) {
+    constexpr int F = OP == 6 ? mx::kFmtE2M1 : OP == 7 ? mx::kFmtE4M3 : mx::kFmtE5M2;
+    const q::f32x2 r = q::cvt_pk_up<F, OP == 6 ? SEL : (SEL & 1)>(au[0], sc);
+    o[0] = q::as_u(r[0]), o[1] = q::as_u(r[1]);
+  }
+  if constexpr (OP == 9 || OP == 10) {
+    const q::u32x6 w = {au[0], au[1], au[2], au[3], au[4], au[5]};
+    const q::f32x32 r = q::cvt_pk32_up<OP == 9 ? mx::kFmtE2M3 : mx::kFmtE3M2>(w, sc);
+    for (int i = 0; i < 32; ++i) o[i] = q::as_u(r[i]);
+  }
+  if constexpr (OP == 11) {
+    const q::f32x2 p = {a[0], a[1]};
+    o[0] = __builtin_amdgcn_cvt_scalef32_sr_pk_fp4_f32(old[l], p, rnd[l], sc, SEL);
+  }
+  if constexpr (OP == 12) o[0] = (unsigned)__builtin_amdgcn_cvt_scalef32_sr_fp8_f32((int)old[l], a[0], rnd[l], sc, SEL);
+}
+template <int OP>
+hipError_t mxq_probe_sel(int sel, const float* src, const unsigned* scale, const unsigned* rnd, const unsigned* old,
+                         unsigned* out, int n, hipStream_t s) {
+  const dim3 g((unsigned)((n + 63) / 64)), b(64);
+  switch (sel) {
+    case 0: hipLaunchKernelGGL((mxq_cvt_probe_kernel<OP, 0>), g, b, 0, s, src, scale, rnd, old, out, n); break;
+    case 1: hipLaunchKernelGGL((mxq_cvt_probe_kernel<OP, 1>), g, b, 0, s, src, scale, rnd, old, out, n); break;
+    case 2: hipLaunchKernelGGL((mxq_cvt_probe_kernel<OP, 2>), g, b, 0, s, src, scale, rnd, old, out, n); break;
+    case 3: hipLaunchKernelGGL((mxq_cvt_probe_kernel<OP, 3>), g, b, 0, s, src, scale, rnd, old, out, n); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
+NTM_API int ntm_mxq_cvt_probe(int op, int sel, const void* src, const void* scale, const void* rnd, const void* old,
+                              void* out, int n, void* stream) {
+  if (!src || !scale || !rnd || !old || !out || n <= 0) return (int)hipErrorInvalidValue;
+  auto* a = (const float*)src;
+  auto *sc = (const unsigned*)scale, *r = (const unsigned*)rnd, *ol = (const unsigned*)old;
+  auto* o = (unsigned*)out;
+  switch (op) {
+#define NTM_MXQ_OP(OP) case OP: return (int)mxq_probe_sel<OP>(sel, a, sc, r, ol, o, n, S(stream));
+    NTM_MXQ_OP(0) NTM_MXQ_OP(1) NTM_MXQ_OP(2) NTM_MXQ_OP(3) NTM_MXQ_OP(4) NTM_MXQ_OP(5) NTM_MXQ_OP(6)
+    NTM_MXQ_OP(7) NTM_MXQ_OP(8) NTM_MXQ_OP(9) NTM_MXQ_OP(10) NTM_MXQ_OP(11) NTM_MXQ_OP(12)
+#undef NTM_MXQ_OP
+  }
+  return (int)hipErrorInvalidValue;
 }

@@ -2,7 +2,7 @@
 // K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep,
 // K6 host-link check, K7 MX block-scaled matrix check, K8 per-XCD sweep,
 // K9 atomics and cross-XCD hand-off check, K10 fp64 / fp32 / fp16 / int8 / sparse
-// matrix-core check).
+// matrix-core check, K11 MX quantise / dequantise).
 // Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
@@ -30,6 +30,7 @@
 #include "ntm/host_link.hpp"
 #include "ntm/mcore.hpp"
 #include "ntm/mx_gemm.hpp"
+#include "ntm/mxq.hpp"
 #include "ntm/xcd_sweep.hpp"
 
 #include "ntm/abi.h"  // NTM_API and the prototype of every export below
@@ -1177,3 +1178,38 @@ NTM_API int ntm_mcore_compare(const void* expected, const void* got, size_t n, i
   return (int)ntm::mc::launch_mcore_compare(expected, got, n, word_bytes, out, S(stream));
 }
 NTM_API int ntm_mcore_mismatch_bytes() { return (int)sizeof(ntm::mc::Mismatch); }
+
+// K11: MX quantise / dequantise on the device with the scaled-conversion instructions
+// (mxq.hpp; rules, generators and messages in mxq_plan.hpp). fmt as K7; dtype 0 fp32,
+// 1 bf16; x / y are [R][ldx] elements of it, packed [R][K * bits / 8] and scales [R][K / 32]
+// as ntm_mx_gemm takes them; rounding 0 = nearest even, 1 = stochastic (e2m1 and e4m3 only,
+// the random word of element i = row * K + k is hash32(seed, 11, i)). ntm_mxq_cvt is the
+// element-level form: it reads the scale bytes instead of choosing them. The
+// ntm_mxq_reference_* twins use integer arithmetic only. K % 32 != 0, ldx < K, a bad format,
+// dtype or rounding mode, a null pointer, packed not 16-byte or scales not 4-byte aligned
+// return hipErrorInvalidValue and launch nothing.
+NTM_API int ntm_mxq_shape_ok(int R, int K, int ldx) { return ntm::mxq::shape_ok(R, K, ldx) ? 1 : 0; }
+NTM_API int ntm_mxq_quantize(int fmt, int src_dtype, const void* x, void* packed, void* scales, int R, int K, int ldx,
+                             int rounding, unsigned long long seed, void* stream) {
+  return (int)ntm::mxq::launch_quantize(false, false, fmt, src_dtype, x, packed, scales, R, K, ldx, rounding, seed, S(stream));
+}
+NTM_API int ntm_mxq_dequantize(int fmt, int dst_dtype, const void* packed, const void* scales, void* y, int R, int K,
+                               int ldx, void* stream) {
+  return (int)ntm::mxq::launch_dequantize(false, fmt, dst_dtype, packed, scales, y, R, K, ldx, S(stream));
+}
+NTM_API int ntm_mxq_cvt(int fmt, int src_dtype, const void* x, const void* scales, void* packed, int R, int K, int ldx,
+                        int rounding, unsigned long long seed, void* stream) {
+  return (int)ntm::mxq::launch_quantize(false, true, fmt, src_dtype, x, packed, const_cast<void*>(scales), R, K, ldx, rounding, seed, S(stream));
+}
+NTM_API int ntm_mxq_reference_quantize(int fmt, int src_dtype, const void* x, void* packed, void* scales, int R, int K,
+                                       int ldx, void* stream) {
+  return (int)ntm::mxq::launch_quantize(true, false, fmt, src_dtype, x, packed, scales, R, K, ldx, 0, 0, S(stream));
+}
+NTM_API int ntm_mxq_reference_dequantize(int fmt, int dst_dtype, const void* packed, const void* scales, void* y, int R,
+                                         int K, int ldx, void* stream) {
+  return (int)ntm::mxq::launch_dequantize(true, fmt, dst_dtype, packed, scales, y, R, K, ldx, S(stream));
+}
+NTM_API int ntm_mxq_reference_cvt(int fmt, int src_dtype, const void* x, const void* scales, void* packed, int R, int K,
+                                  int ldx, void* stream) {
+  return (int)ntm::mxq::launch_quantize(true, true, fmt, src_dtype, x, packed, const_cast<void*>(scales), R, K, ldx, 0, 0, S(stream));
+}

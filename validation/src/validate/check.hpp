@@ -110,6 +110,7 @@ bool run_mx_check(const GpuCtx& g, MxResult& r);         // K7, mx_check.cpp
 bool run_xcd_sweep(const GpuCtx& g, XcdSweepResult& r);  // K8, xcd_sweep.cpp
 bool run_atomics(const GpuCtx& g, AtomicsResult& r);     // K9, atomics.cpp
 bool run_mcore(const GpuCtx& g, McoreResult& r);         // K10, mcore.cpp
+bool run_mxq(const GpuCtx& g, MxqResult& r);             // K11, mxq.cpp
 
 // K1 / K2 and the calls of the above on one GPU (gpu.cpp)
 bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r);

@@ -269,6 +269,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   if (o.xcd_sweep && !run_xcd_sweep(g, r.xcd)) return false;
   if (o.atomics_check && !run_atomics(g, r.atomics)) return false;
   if (o.mcore_check && !run_mcore(g, r.mcore)) return false;
+  if (o.mxq_check && !run_mxq(g, r.mxq)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));

@@ -24,6 +24,9 @@
 //   K10 fp64 / fp32 / fp16 / int8 / 2:4-sparse matrix-core check: every matrix
 //       instruction K1 and K7 never issue, exact answers, off by default
 //       (env NTM_MCORE_CHECK=1; ntm/mcore.hpp)                           mcore.cpp
+//   K11 MX quantise / dequantise on the device with the scaled-conversion
+//       instructions, against integer reference kernels, off by default
+//       (env NTM_MXQ_CHECK=1; ntm/mxq.hpp)                               mxq.cpp
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)                                 collectives.hip
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL  collectives.hip
@@ -74,6 +77,12 @@ int main(int argc, char** argv) {
   if (const char* a = std::getenv("NTM_MCORE_CHECK")) o.mcore_check = std::string(a) == "1";
   if (o.fault == "corrupt_mcore" && !o.mcore_check) {
     std::fprintf(stderr, "fault-inject corrupt_mcore needs NTM_MCORE_CHECK=1\n");
+    usage();
+    return 2;
+  }
+  if (const char* a = std::getenv("NTM_MXQ_CHECK")) o.mxq_check = std::string(a) == "1";
+  if (o.fault == "corrupt_mxq" && !o.mxq_check) {
+    std::fprintf(stderr, "fault-inject corrupt_mxq needs NTM_MXQ_CHECK=1\n");
     usage();
     return 2;
   }

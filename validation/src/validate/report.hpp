@@ -22,6 +22,7 @@
 #include "ntm/cu_sweep_plan.hpp"
 #include "ntm/host_link_plan.hpp"
 #include "ntm/mcore_plan.hpp"
+#include "ntm/mxq_plan.hpp"
 #include "ntm/xcd_sweep_plan.hpp"
 
 #include "json.hpp"
@@ -293,6 +294,33 @@ struct McoreResult {
   static void prometheus(std::ostream& p, const Gpus& res);
 };
 
+// K11 (only with NTM_MXQ_CHECK=1)
+struct MxqResult {
+  bool ran = false;
+  // 32-bit words that differ, per format: conversion sweeps down / up, block quantise (packed
+  // and scale bytes), end to end (e2m1, e2m3 and e4m3 only)
+  unsigned long long bad_down[ntm::mx::kFormats] = {}, bad_up[ntm::mx::kFormats] = {},
+                     bad_block[ntm::mx::kFormats] = {}, bad_e2e[ntm::mx::kFormats] = {};
+  double quantize_gbps = 0;  // fp32 -> e2m1, 8192 x 8192, bytes read + written; reported only
+  double seconds = 0;
+  std::vector<std::string> failures;  // empty = clean
+  unsigned long long bad(int f) const { return bad_down[f] + bad_up[f] + bad_block[f] + bad_e2e[f]; }
+  std::string json() const {
+    if (!ran) return "";
+    std::string names = "[", per;
+    for (int f = 0; f < ntm::mx::kFormats; ++f) {
+      const std::string n = ntm::mx::format_name(f);
+      names += (f ? "," : "") + jstr(n);
+      per += ",\"mxq_" + n + "_down_bad\":" + std::to_string(bad_down[f]) + ",\"mxq_" + n +
+             "_up_bad\":" + std::to_string(bad_up[f]) + ",\"mxq_" + n + "_block_bad\":" + std::to_string(bad_block[f]) +
+             ",\"mxq_" + n + "_e2e_bad\":" + std::to_string(bad_e2e[f]);
+    }
+    return ",\"mxq_formats\":" + names + "]" + per + ",\"mxq_quantize_GBps\":" + jnum(quantize_gbps) +
+           ",\"mxq_seconds\":" + jnum(seconds);
+  }
+  static void prometheus(std::ostream& p, const Gpus& res);
+};
+
 struct GpuResult {
   int device = -1;
   std::string name, arch;
@@ -309,6 +337,7 @@ struct GpuResult {
   XcdSweepResult xcd;
   AtomicsResult atomics;
   McoreResult mcore;
+  MxqResult mxq;
 };
 
 // ------------------------------------------------------------ per-GPU verdicts
@@ -342,7 +371,7 @@ inline std::vector<std::string> gpu_failures(const GpuResult& r, const Opts& o) 
     out.push_back(d + "HBM " + jnum(r.total_gb) + " GB below " + jnum(o.min_hbm_gb) + " GB");
   if (!r.k2.copy_ok) out.push_back(d + "HBM copy mismatch");
   for (const auto* v : {&r.hbm_test.failures, &r.cu_sweep.failures, &r.host_link.failures, &r.mx.failures,
-                        &r.xcd.failures, &r.atomics.failures, &r.mcore.failures})
+                        &r.xcd.failures, &r.atomics.failures, &r.mcore.failures, &r.mxq.failures})
     out.insert(out.end(), v->begin(), v->end());
   if (o.hbm_floor_gbps > 0 && r.k2.copy_gbps < o.hbm_floor_gbps)
     out.push_back(d + "HBM copy " + jnum(r.k2.copy_gbps) + " GB/s below floor");
@@ -563,6 +592,21 @@ inline void McoreResult::prometheus(std::ostream& p, const Gpus& res) {
           << jnum(r.mcore.rate(f)) << "\n";
 }
 
+inline void MxqResult::prometheus(std::ostream& p, const Gpus& res) {
+  p << "# HELP amdgpu_validate_mxq_bad Words of the MX quantise check that differ from the reference kernels.\n"
+    << "# TYPE amdgpu_validate_mxq_bad gauge\n";
+  for (auto& r : res)
+    for (int f = 0; r.mxq.ran && f < ntm::mx::kFormats; ++f)
+      p << "amdgpu_validate_mxq_bad{gpu=\"" << r.device << "\",format=\"" << ntm::mx::format_name(f) << "\"} "
+        << r.mxq.bad(f) << "\n";
+  auto ran = [](const GpuResult& r) { return r.mxq.ran; };
+  gauge(p, res, "amdgpu_validate_mxq_quantize_gbps",
+        "fp32 to MXFP4 quantise of 8192 x 8192, GB/s of bytes read and written (reported only).", ran,
+        [](const GpuResult& r) { return jnum(r.mxq.quantize_gbps); });
+  gauge(p, res, "amdgpu_validate_mxq_seconds", "Seconds the MX quantise check took.", ran,
+        [](const GpuResult& r) { return jnum(r.mxq.seconds); });
+}
+
 // node-exporter textfile-collector format (--prom-out) and Pushgateway body
 // (--pushgateway); labels carry the device index.
 inline std::string prometheus_text(const Report& R) {
@@ -590,6 +634,7 @@ inline std::string prometheus_text(const Report& R) {
   if (o.mx_check) MxResult::prometheus(p, R.gpus);
   if (o.atomics_check) AtomicsResult::prometheus(p, R.gpus);
   if (o.mcore_check) McoreResult::prometheus(p, R.gpus);
+  if (o.mxq_check) MxqResult::prometheus(p, R.gpus);
   if (!R.rccl_rows.empty() || !R.xgmi_rows.empty())
     p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
       << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(Report::peak_any(R.rccl_rows)) << "\n"
@@ -620,7 +665,7 @@ inline std::string report_json(const Report& R) {
     js += (i ? "," : "") + std::string("{\"device\":") + std::to_string(r.device) +
           ",\"name\":" + jstr(r.name) + ",\"arch\":" + jstr(r.arch) + ",\"hbm_total_gb\":" + jnum(r.total_gb) +
           r.k1.json() + r.fp8.json() + r.sk.json() + r.k2.json() + r.hbm_test.json() + r.cu_sweep.json() +
-          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + "}";
+          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + r.mxq.json() + "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(R.rccl_rows);
   js += ",\"xgmi_allreduce_bf16\":" + coll_json(R.xgmi_rows);
