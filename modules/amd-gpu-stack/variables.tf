@@ -381,6 +381,12 @@ variable "validation_mxq_check" {
   description = "Run the Job's device-side MX quantise / dequantise check (K11): the gfx950 scaled-conversion instructions quantise fp32 and bf16 to e4m3, e5m2, e2m3, e3m2 and e2m1 with an E8M0 scale per 32 elements (OCP MX v1.0) and back, compared bitwise with reference kernels that use integer arithmetic only - conversion sweeps over every rounding boundary, every finite bf16 code and every code at every scale byte, a block quantise of a 1024 x 4096 matrix, and an end-to-end product of operands quantised on the device through the K7 GEMM; the quantise rate is reported. A wrong word fails the Job by format, sub-test, row and element. It sets NTM_MXQ_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/mxq/README.md."
 }
 
+variable "validation_wave_check" {
+  type        = bool
+  default     = false
+  description = "Run the Job's wave data-path and special-function check (K12): on every CU the DPP modifiers, ds_bpermute / ds_permute, ds_swizzle, the permlane16 / permlane32 swaps and v_readlane / v_readfirstlane on hashed words, the gfx950 transposed LDS reads (16-, 8-, 4- and 6-bit), v_bitop3_b32 over all 256 truth tables and v_cvt_pk_bf16_f32, each compared bitwise with a reference kernel that uses none of those instructions, and the fp32 transcendentals (exp, log, rcp, rsq, sqrt, sin, cos), whose results must agree across all workgroups and are measured against brackets the host computes in long double. A wrong word fails the Job by XCD, SE, SH, CU, SIMD, family, op and lane. It sets NTM_WAVE_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/wave/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

@@ -32,6 +32,11 @@ K11 ``mx_quantize``, ``mx_dequantize``, ``mxq_cvt`` - MX quantise / dequantise o
    ``mx_quantize_reference_gpu``, ``mx_dequantize_reference_gpu`` - the same by integer
    arithmetic; ``mxq_quantize_bits``, ``mxq_dequantize_bits``, ``mxq_make_inputs`` - the host
    side (numpy, ``ops.mxq``).
+K12 ``wave_lane``, ``wave_tr_read``, ``wave_sfu``, ``wave_sfu_digest``, ``wave_sfu_distance``,
+   ``wave_sfu_locate``, ``wave_valu``, ``wave_sweep`` - cross-lane movement, the gfx950 transposed LDS reads, the fp32
+   transcendentals and v_bitop3 / v_cvt_pk_bf16 on the device; ``wave_lane_reference_gpu``,
+   ``wave_tr_read_reference_gpu`` - the same without the instructions under test;
+   ``wave_expected_*``, ``wave_sfu_inputs``, ``wave_sfu_brackets`` - the host side (numpy, ``ops.wave``).
 K3 ``fill_uniform_``, ``ref_gemm_f32``, ``verify_bf16``, ``abft_check`` - synthetic
    data, full fp32 reference check and the O(n^2) checksum check;
    ``clock_probe_ghz`` - the shader clock held under a dense MFMA load;
@@ -125,6 +130,44 @@ from .kernels import (  # noqa: F401
     mxq_cvt,
     mxq_to_device,
     verify_bf16,
+    wave_cu_key,
+    wave_lane,
+    wave_lane_reference_gpu,
+    wave_sfu,
+    wave_sfu_digest,
+    wave_sfu_distance,
+    wave_sfu_locate,
+    wave_sweep,
+    wave_to_device,
+    wave_tr_read,
+    wave_tr_read_reference_gpu,
+    wave_valu,
+)
+from .wave import (  # noqa: F401
+    WAVE_FAMILIES,
+    WAVE_FAULT_BIT,
+    WAVE_SFU_BOUND,
+    WAVE_SFU_OPS,
+    WAVE_TR_BITS,
+    wave_bf16_rne,
+    wave_bpermute_index,
+    wave_cvt_inputs,
+    wave_expected_bitop3,
+    wave_expected_cvt_pk,
+    wave_expected_lane,
+    wave_expected_sfu_distance,
+    wave_expected_tr_read,
+    wave_failure_message,
+    wave_hash32,
+    wave_lane_op_index,
+    wave_lane_op_name,
+    wave_lane_ops,
+    wave_make_image,
+    wave_sfu_brackets,
+    wave_sfu_inputs,
+    wave_src_lane,
+    wave_tr_shape,
+    wave_tr_src,
 )
 from .mxq import (  # noqa: F401
     MXQ_EMAX,

@@ -176,6 +176,17 @@ SIGNATURES = {
     "ntm_mxq_reference_quantize": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
     "ntm_mxq_reference_dequantize": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
     "ntm_mxq_reference_cvt": ([c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp], c_int),
+    "ntm_wave_lane_ops": ([], c_int),
+    "ntm_wave_record_bytes": ([], c_int),
+    "ntm_wave_lane": ([c_int, c_int, c_int, c_vp, c_vp, c_vp, c_size, c_vp], c_int),
+    "ntm_wave_tr_out_words": ([c_int, c_int, c_int], c_int),
+    "ntm_wave_tr_read": ([c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp], c_int),
+    "ntm_wave_sfu": ([c_int, c_vp, c_vp, c_size, c_vp], c_int),
+    "ntm_wave_sfu_distance": ([c_vp, c_vp, c_vp, c_size, ctypes.c_uint, c_vp, c_vp], c_int),
+    "ntm_wave_sfu_locate": ([c_int, c_vp, ctypes.c_uint, ctypes.c_uint, c_int, c_vp, c_vp, c_vp, c_int, ctypes.c_uint,
+                             ctypes.c_uint, c_vp], c_int),
+    "ntm_wave_valu": ([c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_size, c_vp], c_int),
+    "ntm_wave_sweep": ([c_int, c_vp, c_size, c_vp, c_vp, c_vp, c_int, ctypes.c_uint, ctypes.c_uint, c_vp], c_int),
 }
 
 XGMI_SIGNATURES = {
@@ -233,6 +244,7 @@ def _declare_experimental(lib: ctypes.CDLL) -> None:
         "ntm_mx_mfma_probe": ([c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp], c_int),
         "ntm_mcore_mfma_probe": ([c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp], c_int),
         "ntm_mxq_cvt_probe": ([c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp], c_int),
+        "ntm_wave_tr_probe": ([c_int, c_vp, c_vp, c_vp, c_vp], c_int),
         "ntm_mfma_rate": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_mfma_toggle": ([c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
         "ntm_dma_probe": ([c_int, c_vp, c_int, c_int, c_int, c_int, c_vp], c_int),

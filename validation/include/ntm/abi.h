@@ -174,6 +174,18 @@ NTM_API int ntm_mxq_reference_quantize(int fmt, int src_dtype, const void* x, vo
 NTM_API int ntm_mxq_reference_dequantize(int fmt, int dst_dtype, const void* packed, const void* scales, void* y, int R, int K, int ldx, void* stream);
 NTM_API int ntm_mxq_reference_cvt(int fmt, int src_dtype, const void* x, const void* scales, void* packed, int R, int K, int ldx, void* stream);
 
+/* ---- K12 wave data-path and special-function check (ntm/wave_paths.hpp, ntm/wave_paths_plan.hpp) */
+NTM_API int ntm_wave_lane_ops(void);
+NTM_API int ntm_wave_record_bytes(void);
+NTM_API int ntm_wave_lane(int reference, int op_first, int op_count, const void* x, const void* y, void* out, size_t n, void* stream);
+NTM_API int ntm_wave_tr_out_words(int bits, int rows, int stride);
+NTM_API int ntm_wave_tr_read(int reference, int bits, const void* image, int rows, int stride, void* out, void* stream);
+NTM_API int ntm_wave_sfu(int op, const void* x, void* y, size_t n, void* stream);
+NTM_API int ntm_wave_sfu_distance(const void* y, const void* lo, const void* hi, size_t n, unsigned bound, void* out, void* stream);
+NTM_API int ntm_wave_sfu_locate(int op, const void* x, unsigned n, unsigned cu_key, int on_key, void* claim, void* y, void* record, int grid, unsigned fault_key, unsigned fault_index, void* stream);
+NTM_API int ntm_wave_valu(int reference, int op, const void* a, const void* b, const void* c, void* out, size_t n, void* stream);
+NTM_API int ntm_wave_sweep(int family, const void* in, size_t in_words, const unsigned* layout, const void* expected, void* records, int grid, unsigned fault_wg, unsigned fault_index, void* stream);
+
 /* ---- C2 hand-written xGMI all-reduce (xgmi_allreduce.hip, ntm/xgmi_allreduce.hpp)
  * and the allocation / HIP IPC helpers its Python side needs */
 NTM_API int ntm_xgmi_allreduce_bf16(const void* const* in_ptrs, void* const* out_ptrs, unsigned* const* sig_ptrs, int nranks, int rank_base, int nranks_here, int nblk, size_t count, unsigned epoch, unsigned* err, int one_shot, void* stream);

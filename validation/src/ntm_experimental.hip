@@ -37,6 +37,7 @@
 #include "ntm/mx_gemm.hpp"
 #include "ntm/mxq.hpp"
 #include "ntm/stream_policy_exp.hpp"
+#include "ntm/wave_paths.hpp"
 
 #include "ntm/abi.h"  // NTM_API; this file's own exports are for tests only and are declared here
 
@@ -448,4 +449,37 @@ NTM_API int ntm_mxq_cvt_probe(int op, int sel, const void* src, const void* scal
 #undef NTM_MXQ_OP
   }
   return (int)hipErrorInvalidValue;
+}
+
+// K12 transposed-read probe: one ds_read_b64_tr_b16 / _tr_b8 / _tr_b4 or ds_read_b96_tr_b6 by one
+// wave on a caller-built 4 KiB LDS image (tools/wave_lane_map_probe.py). Lane l reads at byte
+// address addr[l], forced into the image and to a multiple of 8, and writes its 3 result dwords
+// (the third is 0 for the b64 forms) to out[3 l ..].
+namespace {
+template <int BITS>
+__global__ void __launch_bounds__(64) wave_tr_probe_kernel(const uint32_t* image, const uint32_t* addr, uint32_t* out) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4096];
+  const int l = threadIdx.x;
+  for (int i = l; i < 1024; i += 64) ((uint32_t*)lds)[i] = image[i];
+  __syncthreads();
+  unsigned a = addr[l] & 0xFF8u;
+  if (a > 4096u - 16u) a = 4096u - 16u;
+  uint32_t r[3];
+  ntm::wave::tr_read<BITS>(lds + a, r);
+  for (int d = 0; d < 3; ++d) out[3 * l + d] = r[d];
+}
+}  // namespace
+
+NTM_API int ntm_wave_tr_probe(int bits, const void* image, const void* addr, void* out, void* stream) {
+  if (!image || !addr || !out) return (int)hipErrorInvalidValue;
+  auto *im = (const uint32_t*)image, *ad = (const uint32_t*)addr;
+  auto* o = (uint32_t*)out;
+  switch (bits) {
+    case 16: hipLaunchKernelGGL(wave_tr_probe_kernel<16>, dim3(1), dim3(64), 0, S(stream), im, ad, o); break;
+    case 8: hipLaunchKernelGGL(wave_tr_probe_kernel<8>, dim3(1), dim3(64), 0, S(stream), im, ad, o); break;
+    case 4: hipLaunchKernelGGL(wave_tr_probe_kernel<4>, dim3(1), dim3(64), 0, S(stream), im, ad, o); break;
+    case 6: hipLaunchKernelGGL(wave_tr_probe_kernel<6>, dim3(1), dim3(64), 0, S(stream), im, ad, o); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
 }

@@ -2,7 +2,7 @@
 // K3 fill/reference/verify, K4 HBM pattern test, K5 per-CU compute sweep,
 // K6 host-link check, K7 MX block-scaled matrix check, K8 per-XCD sweep,
 // K9 atomics and cross-XCD hand-off check, K10 fp64 / fp32 / fp16 / int8 / sparse
-// matrix-core check, K11 MX quantise / dequantise).
+// matrix-core check, K11 MX quantise / dequantise, K12 wave data paths and special functions).
 // Built for gfx950 only into
 //   nvidia_terraform_modules_amd/ops/libntm_validation.so   (Python, ctypes)
 //   validation/build/amdgpu-validate                        (Job entrypoint)
@@ -31,6 +31,7 @@
 #include "ntm/mcore.hpp"
 #include "ntm/mx_gemm.hpp"
 #include "ntm/mxq.hpp"
+#include "ntm/wave_paths.hpp"
 #include "ntm/xcd_sweep.hpp"
 
 #include "ntm/abi.h"  // NTM_API and the prototype of every export below
@@ -1212,4 +1213,58 @@ NTM_API int ntm_mxq_reference_dequantize(int fmt, int dst_dtype, const void* pac
 NTM_API int ntm_mxq_reference_cvt(int fmt, int src_dtype, const void* x, const void* scales, void* packed, int R, int K,
                                   int ldx, void* stream) {
   return (int)ntm::mxq::launch_quantize(true, true, fmt, src_dtype, x, packed, const_cast<void*>(scales), R, K, ldx, 0, 0, S(stream));
+}
+
+// K12: wave data-path and special-function check (wave_paths.hpp; op list, maps, generators,
+// records and messages in wave_paths_plan.hpp). `reference` != 0 runs the kernel that uses none
+// of the instructions under test. Buffers are 32-bit words, 4-byte aligned (a transposed-read
+// image 16-byte aligned); a null or misaligned pointer, a bad op / form / family id or a bad
+// shape returns hipErrorInvalidValue and launches nothing.
+//   ntm_wave_lane      ops op_first .. op_first + op_count - 1 of the lane list on x[n], y[n]
+//                      (n a multiple of 256; each 64 words are one wave) -> out[k * n + i]
+//   ntm_wave_tr_read   one workgroup reads an image of rows x stride bytes through the
+//                      bits-wide transposed read -> out[ntm_wave_tr_out_words()]
+//   ntm_wave_sfu       y[i] = the instruction op on x[i]
+//   ntm_wave_sfu_distance  largest ordered-integer distance of y[i] from [lo[i], hi[i]], its
+//                      index, the count beyond `bound` and the first such index -> out (16 bytes,
+//                      initialised max 0 / all ones / 0 / all ones)
+//   ntm_wave_sfu_locate  the second launch behind an inconsistent digest: the first of `grid`
+//                      workgroups that runs on the CU cu_key (on_key != 0; else on any other CU)
+//                      sets *claim (zeroed by the caller), stores the instruction's words on
+//                      x[n] to y and fills *record
+//   ntm_wave_valu      op 0: out[table * n + i] = bitop3(a, b, c) for the 256 tables; op 1:
+//                      out[i] = bf16(a[i]) | bf16(b[i]) << 16
+//   ntm_wave_sweep     the per-CU form: `grid` workgroups each run the whole family against
+//                      `expected` and leave one Record (layout of `in`: wave_paths.hpp)
+NTM_API int ntm_wave_lane_ops() { return ntm::wave::kLaneOps; }
+NTM_API int ntm_wave_record_bytes() { return (int)sizeof(ntm::wave::Record); }
+NTM_API int ntm_wave_lane(int reference, int op_first, int op_count, const void* x, const void* y, void* out, size_t n,
+                          void* stream) {
+  return (int)ntm::wave::launch_lane(reference != 0, op_first, op_count, x, y, out, n, S(stream));
+}
+NTM_API int ntm_wave_tr_out_words(int bits, int rows, int stride) {
+  ntm::wave::TrShape s;
+  return ntm::wave::tr_shape(bits, rows, stride, &s) ? (int)ntm::wave::tr_out_words(s) : 0;
+}
+NTM_API int ntm_wave_tr_read(int reference, int bits, const void* image, int rows, int stride, void* out, void* stream) {
+  return (int)ntm::wave::launch_tr_read(reference != 0, bits, image, rows, stride, out, S(stream));
+}
+NTM_API int ntm_wave_sfu(int op, const void* x, void* y, size_t n, void* stream) {
+  return (int)ntm::wave::launch_sfu(op, x, y, n, S(stream));
+}
+NTM_API int ntm_wave_sfu_distance(const void* y, const void* lo, const void* hi, size_t n, unsigned bound, void* out,
+                                  void* stream) {
+  return (int)ntm::wave::launch_sfu_distance(y, lo, hi, n, bound, out, S(stream));
+}
+NTM_API int ntm_wave_sfu_locate(int op, const void* x, unsigned n, unsigned cu_key, int on_key, void* claim, void* y,
+                                void* record, int grid, unsigned fault_key, unsigned fault_index, void* stream) {
+  return (int)ntm::wave::launch_sfu_locate(op, x, n, cu_key, on_key, claim, y, record, grid, fault_key, fault_index, S(stream));
+}
+NTM_API int ntm_wave_valu(int reference, int op, const void* a, const void* b, const void* c, void* out, size_t n,
+                          void* stream) {
+  return (int)ntm::wave::launch_valu(reference != 0, op, a, b, c, out, n, S(stream));
+}
+NTM_API int ntm_wave_sweep(int family, const void* in, size_t in_words, const unsigned* layout, const void* expected,
+                           void* records, int grid, unsigned fault_wg, unsigned fault_index, void* stream) {
+  return (int)ntm::wave::launch_sweep(family, in, in_words, layout, expected, records, grid, fault_wg, fault_index, S(stream));
 }

@@ -270,6 +270,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   if (o.atomics_check && !run_atomics(g, r.atomics)) return false;
   if (o.mcore_check && !run_mcore(g, r.mcore)) return false;
   if (o.mxq_check && !run_mxq(g, r.mxq)) return false;
+  if (o.wave_check && !run_wave(g, r.wave)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));

@@ -27,6 +27,9 @@
 //   K11 MX quantise / dequantise on the device with the scaled-conversion
 //       instructions, against integer reference kernels, off by default
 //       (env NTM_MXQ_CHECK=1; ntm/mxq.hpp)                               mxq.cpp
+//   K12 wave data paths (DPP, permutes, swizzle, lane swaps, transposed LDS
+//       reads), the special-function unit and the gfx950 VALU additions, per
+//       CU, off by default (env NTM_WAVE_CHECK=1; ntm/wave_paths.hpp)    wave.cpp
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)                                 collectives.hip
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL  collectives.hip
@@ -83,6 +86,12 @@ int main(int argc, char** argv) {
   if (const char* a = std::getenv("NTM_MXQ_CHECK")) o.mxq_check = std::string(a) == "1";
   if (o.fault == "corrupt_mxq" && !o.mxq_check) {
     std::fprintf(stderr, "fault-inject corrupt_mxq needs NTM_MXQ_CHECK=1\n");
+    usage();
+    return 2;
+  }
+  if (const char* a = std::getenv("NTM_WAVE_CHECK")) o.wave_check = std::string(a) == "1";
+  if ((o.fault == "corrupt_wave" || o.fault == "corrupt_wave_sfu") && !o.wave_check) {
+    std::fprintf(stderr, "fault-inject %s needs NTM_WAVE_CHECK=1\n", o.fault.c_str());
     usage();
     return 2;
   }

@@ -23,6 +23,7 @@
 #include "ntm/host_link_plan.hpp"
 #include "ntm/mcore_plan.hpp"
 #include "ntm/mxq_plan.hpp"
+#include "ntm/wave_paths_plan.hpp"
 #include "ntm/xcd_sweep_plan.hpp"
 
 #include "json.hpp"
@@ -321,6 +322,33 @@ struct MxqResult {
   static void prometheus(std::ostream& p, const Gpus& res);
 };
 
+// K12 (only with NTM_WAVE_CHECK=1)
+struct WaveResult {
+  bool ran = false;
+  uint32_t cus = 0, cus_covered = 0;  // CUs that ran every family
+  // result words that differ from the reference kernels' tables, over all workgroups
+  unsigned long long lane_bad = 0, ldstr_bad = 0, valu_bad = 0;
+  unsigned long long sfu_inconsistent = 0;  // (workgroup, instruction) digests off the majority's
+  uint32_t sfu_max_d[ntm::wave::kSfuOps] = {}, sfu_max_x[ntm::wave::kSfuOps] = {};  // largest distance, its input
+  unsigned long long sfu_beyond = 0;        // results beyond a recorded bound
+  double seconds = 0;
+  std::vector<std::string> failures;  // empty = clean
+  std::string json() const {
+    if (!ran) return "";
+    std::string d = "{";
+    for (int op = 0; op < ntm::wave::kSfuOps; ++op)
+      d += std::string(op ? "," : "") + jstr(ntm::wave::sfu_name(op)) + ":{\"d\":" + std::to_string(sfu_max_d[op]) +
+           ",\"input\":" + jstr(ntm::wave::hex32(sfu_max_x[op])) + ",\"judged\":" +
+           (ntm::wave::kSfuBound[op] != ntm::wave::kSfuNoBound ? "true" : "false") + "}";
+    return ",\"wave_lane_bad\":" + std::to_string(lane_bad) + ",\"wave_ldstr_bad\":" + std::to_string(ldstr_bad) +
+           ",\"wave_valu_bad\":" + std::to_string(valu_bad) + ",\"wave_sfu_inconsistent\":" +
+           std::to_string(sfu_inconsistent) + ",\"wave_sfu_max_distance\":" + d + "}" + ",\"wave_sfu_beyond_bound\":" +
+           std::to_string(sfu_beyond) + ",\"wave_cus_covered\":" + std::to_string(cus_covered) +
+           ",\"wave_seconds\":" + jnum(seconds);
+  }
+  static void prometheus(std::ostream& p, const Gpus& res);
+};
+
 struct GpuResult {
   int device = -1;
   std::string name, arch;
@@ -338,6 +366,7 @@ struct GpuResult {
   AtomicsResult atomics;
   McoreResult mcore;
   MxqResult mxq;
+  WaveResult wave;
 };
 
 // ------------------------------------------------------------ per-GPU verdicts
@@ -371,7 +400,7 @@ inline std::vector<std::string> gpu_failures(const GpuResult& r, const Opts& o) 
     out.push_back(d + "HBM " + jnum(r.total_gb) + " GB below " + jnum(o.min_hbm_gb) + " GB");
   if (!r.k2.copy_ok) out.push_back(d + "HBM copy mismatch");
   for (const auto* v : {&r.hbm_test.failures, &r.cu_sweep.failures, &r.host_link.failures, &r.mx.failures,
-                        &r.xcd.failures, &r.atomics.failures, &r.mcore.failures, &r.mxq.failures})
+                        &r.xcd.failures, &r.atomics.failures, &r.mcore.failures, &r.mxq.failures, &r.wave.failures})
     out.insert(out.end(), v->begin(), v->end());
   if (o.hbm_floor_gbps > 0 && r.k2.copy_gbps < o.hbm_floor_gbps)
     out.push_back(d + "HBM copy " + jnum(r.k2.copy_gbps) + " GB/s below floor");
@@ -607,6 +636,21 @@ inline void MxqResult::prometheus(std::ostream& p, const Gpus& res) {
         [](const GpuResult& r) { return jnum(r.mxq.seconds); });
 }
 
+inline void WaveResult::prometheus(std::ostream& p, const Gpus& res) {
+  p << "# HELP amdgpu_validate_wave_bad Results of the wave data-path check that differ from the reference kernels.\n"
+    << "# TYPE amdgpu_validate_wave_bad gauge\n";
+  for (auto& r : res) {
+    if (!r.wave.ran) continue;
+    const unsigned long long bad[ntm::wave::kFamilies] = {r.wave.lane_bad, r.wave.ldstr_bad,
+                                                          r.wave.sfu_inconsistent + r.wave.sfu_beyond, r.wave.valu_bad};
+    for (int f = 0; f < ntm::wave::kFamilies; ++f)
+      p << "amdgpu_validate_wave_bad{gpu=\"" << r.device << "\",family=\"" << ntm::wave::family_name(f) << "\"} " << bad[f]
+        << "\n";
+  }
+  gauge(p, res, "amdgpu_validate_wave_seconds", "Seconds the wave data-path check took.",
+        [](const GpuResult& r) { return r.wave.ran; }, [](const GpuResult& r) { return jnum(r.wave.seconds); });
+}
+
 // node-exporter textfile-collector format (--prom-out) and Pushgateway body
 // (--pushgateway); labels carry the device index.
 inline std::string prometheus_text(const Report& R) {
@@ -635,6 +679,7 @@ inline std::string prometheus_text(const Report& R) {
   if (o.atomics_check) AtomicsResult::prometheus(p, R.gpus);
   if (o.mcore_check) McoreResult::prometheus(p, R.gpus);
   if (o.mxq_check) MxqResult::prometheus(p, R.gpus);
+  if (o.wave_check) WaveResult::prometheus(p, R.gpus);
   if (!R.rccl_rows.empty() || !R.xgmi_rows.empty())
     p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
       << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(Report::peak_any(R.rccl_rows)) << "\n"
@@ -665,7 +710,7 @@ inline std::string report_json(const Report& R) {
     js += (i ? "," : "") + std::string("{\"device\":") + std::to_string(r.device) +
           ",\"name\":" + jstr(r.name) + ",\"arch\":" + jstr(r.arch) + ",\"hbm_total_gb\":" + jnum(r.total_gb) +
           r.k1.json() + r.fp8.json() + r.sk.json() + r.k2.json() + r.hbm_test.json() + r.cu_sweep.json() +
-          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + r.mxq.json() + "}";
+          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + r.mxq.json() + r.wave.json() + "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(R.rccl_rows);
   js += ",\"xgmi_allreduce_bf16\":" + coll_json(R.xgmi_rows);
