@@ -15,8 +15,17 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .kernels import (AbftReport, HbmPatternReport, VerifyReport, gemm_shape_ok,  # noqa: F401
-                      gemm_tolerance, hbm_pattern_check_args, hbm_pattern_id)
+from . import mcore as _mcore
+from . import mx as _mx
+from .gpu.hbm_pattern import HbmPatternReport, hbm_pattern_check_args, hbm_pattern_id
+from .gpu.mcore import McoreCompareReport, mcore_check_args
+from .gpu.mcore import mcore_to_device as _mcore_to_device
+from .gpu.mx import MxCompareReport, mx_check_args
+from .kernels import AbftReport, VerifyReport, gemm_shape_ok, gemm_tolerance  # noqa: F401
+from .mcore import (MCORE_FORMATS, mcore_compress, mcore_decode_windows, mcore_exact,  # noqa: F401
+                    mcore_expand, mcore_failure_message, mcore_make_inputs, mcore_matmul_bits,
+                    mcore_max_abits)
+from .mx import mx_dense_exact, mx_make_inputs, mx_matmul_bits, mx_pack, mx_unpack  # noqa: F401
 
 
 def fill_uniform_(t: torch.Tensor, seed: int, scale: float = 1.0) -> torch.Tensor:
@@ -300,12 +309,6 @@ def cu_sweep_expected(iters: int, seed: int, lds_bytes: int) -> dict:
 
 # K7 on the CPU: the MX check's products come from the exact integer reference in ops/mx.py
 # (table decode, integer dot); tensors are CPU uint8 / fp32, nothing runs on a matrix core.
-from . import mx as _mx  # noqa: E402
-from .kernels import MxCompareReport, mx_check_args  # noqa: E402
-from .mx import (mx_dense_exact, mx_make_inputs, mx_matmul_bits, mx_pack,  # noqa: E402,F401
-                 mx_unpack)
-
-
 def mx_gemm(a, b, sa, sb, fmt, out: torch.Tensor | None = None) -> torch.Tensor:
     mx_check_args(a, b, sa, sb, fmt, out, need_cuda=False)
     bits = _mx.mx_matmul_bits(a.numpy(), b.numpy(), sa.numpy(), sb.numpy(), fmt)
@@ -319,34 +322,24 @@ def mx_gemm(a, b, sa, sb, fmt, out: torch.Tensor | None = None) -> torch.Tensor:
 mx_reference_gpu = mx_gemm
 
 
-def mx_compare(expected: torch.Tensor, got: torch.Tensor) -> MxCompareReport:
-    e = _bytes_of(expected).view(np.uint32)
-    g = _bytes_of(got).view(np.uint32)
+def _compare(expected: torch.Tensor, got: torch.Tensor, word, what: str) -> MxCompareReport:   # = McoreCompareReport
+    e = _bytes_of(expected).view(word)
+    g = _bytes_of(got).view(word)
     if e.size != g.size:
-        raise ValueError("mx_compare needs two tensors of one size")
+        raise ValueError(f"{what} needs two tensors of one size")
     idx = np.flatnonzero(e != g)
     if not idx.size:
         return MxCompareReport(0, None, None, None)
     return MxCompareReport(int(idx.size), int(idx[0]), int(e[idx[0]]), int(g[idx[0]]))
 
 
+def mx_compare(expected: torch.Tensor, got: torch.Tensor) -> MxCompareReport:
+    return _compare(expected, got, np.uint32, "mx_compare")
+
 
 # K10 on the CPU: every product is the exact numpy reference (ops/mcore.py)
-from . import mcore as _mcore  # noqa: E402
-from .kernels import McoreCompareReport, mcore_check_args  # noqa: E402
-from .mcore import (MCORE_FORMATS, mcore_compress, mcore_decode_windows, mcore_exact,  # noqa: E402,F401
-                    mcore_expand, mcore_failure_message, mcore_make_inputs, mcore_matmul_bits,
-                    mcore_max_abits)
-
-
 def mcore_to_device(inputs: dict, device) -> dict:
-    def t(x):
-        if x is None:
-            return None
-        if x.dtype == np.uint16:
-            return torch.from_numpy(x.view(np.int16).copy()).view(torch.bfloat16)
-        return torch.from_numpy(x.copy())
-    return {**inputs, "a": t(inputs["a"]), "ai": t(inputs["ai"]), "b": t(inputs["b"])}
+    return _mcore_to_device(inputs, "cpu")
 
 
 def mcore_gemm(a, b, fmt, ai=None, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -368,12 +361,4 @@ mcore_reference_gpu = mcore_gemm
 
 
 def mcore_compare(expected: torch.Tensor, got: torch.Tensor) -> McoreCompareReport:
-    word = np.uint64 if expected.element_size() == 8 else np.uint32
-    e = _bytes_of(expected).view(word)
-    g = _bytes_of(got).view(word)
-    if e.size != g.size:
-        raise ValueError("mcore_compare needs two tensors of one size")
-    idx = np.flatnonzero(e != g)
-    if not idx.size:
-        return McoreCompareReport(0, None, None, None)
-    return McoreCompareReport(int(idx.size), int(idx[0]), int(e[idx[0]]), int(g[idx[0]]))
+    return _compare(expected, got, np.uint64 if expected.element_size() == 8 else np.uint32, "mcore_compare")

@@ -111,7 +111,7 @@ def test_injected_fault_is_pinned_to_its_cu_and_subtest(ops, clean_launch, subte
 
 
 def test_argument_refusals_launch_nothing(ops, monkeypatch):
-    from nvidia_terraform_modules_amd.ops import kernels
+    from nvidia_terraform_modules_amd.ops.gpu import cu_sweep as kernels
 
     class NoLaunch:
         def __getattr__(self, name):

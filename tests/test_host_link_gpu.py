@@ -144,7 +144,7 @@ def test_c_abi_refuses_unmapped_memory_and_bad_sizes():
     plain = np.zeros(1 << 14, dtype=np.uint8)                   # pageable: not mapped
     p = plain.ctypes.data + (-plain.ctypes.data) % 64
     whole, host = _pinned(4096)
-    res = ops.kernels.new_pattern_result("cuda")
+    res = ops.gpu.hbm_pattern.new_pattern_result("cuda")
     out = torch.zeros(3, dtype=torch.int64, device="cuda")
     bad = HIP_ERROR_INVALID_VALUE
     assert L.ntm_host_link_push(p, 4096, 0, 1, 0, 0, 0, s) == bad

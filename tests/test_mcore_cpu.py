@@ -215,7 +215,7 @@ def test_ops_refuse_cpu_tensors_and_bad_shapes():
         ops.mcore_reference_gpu(i["a"], i["b"], "sp_i8", i["ai"])
     with pytest.raises(ValueError, match="needs GPU tensors"):
         ops.mcore_compare(torch.zeros(4), torch.zeros(4))
-    check = ops.kernels.mcore_check_args
+    check = ops.gpu.mcore.mcore_check_args
     assert check(i["a"], i["b"], "sp_i8", i["ai"], need_cuda=False) == (5, 128, 128, 128)
     with pytest.raises(ValueError, match="ai"):
         check(i["a"], i["b"], "sp_i8", None, need_cuda=False)

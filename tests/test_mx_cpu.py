@@ -214,7 +214,7 @@ def test_ops_refuse_cpu_tensors_and_bad_shapes():
             fn(t["a"], t["b"], t["sa"], t["sb"], "e2m1")
     with pytest.raises(ValueError, match="needs GPU tensors"):
         ops.mx_compare(torch.zeros(4), torch.zeros(4))
-    check = lambda *a, **k: ops.kernels.mx_check_args(*a, need_cuda=False, **k)  # noqa: E731
+    check = lambda *a, **k: ops.gpu.mx.mx_check_args(*a, need_cuda=False, **k)  # noqa: E731
     assert check(t["a"], t["b"], t["sa"], t["sb"], "e2m1") == (4, 128, 128, 128)
     with pytest.raises(ValueError, match="multiples of 128"):
         check(t["a"][:64], t["b"], t["sa"][:64], t["sb"], "e2m1")

@@ -21,7 +21,8 @@ import torch
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 from nvidia_terraform_modules_amd import ops  # noqa: E402
-from nvidia_terraform_modules_amd.ops import kernels, reference  # noqa: E402
+from nvidia_terraform_modules_amd.ops import reference  # noqa: E402
+from nvidia_terraform_modules_amd.ops.gpu import cu_sweep as k5  # noqa: E402
 from nvidia_terraform_modules_amd.ops._lib import lib, stream_handle  # noqa: E402
 
 BIN = ROOT / "validation" / "build" / "amdgpu-validate"
@@ -37,7 +38,7 @@ def coverage(cus, iters, trials):
     for t in range(trials):
         recs, launches = [], 0
         first = None
-        while launches < kernels.CU_SWEEP_MAX_LAUNCHES:
+        while launches < k5.CU_SWEEP_MAX_LAUNCHES:
             recs.append(ops.cu_sweep("cuda:0", iters=iters, seed=launches))
             launches += 1
             s = ops.cu_sweep_summarize(np.concatenate(recs), cus, launches)
@@ -110,7 +111,7 @@ def main():
     out["launch_rc_at_attribute_plus_16"] = over
     out["coverage"] = coverage(cus, a.iters, a.trials)
     print(json.dumps({"coverage": out["coverage"]}), flush=True)
-    grid = kernels.CU_SWEEP_GRID_PER_CU * cus
+    grid = k5.CU_SWEEP_GRID_PER_CU * cus
     timing = []
     for it in sorted({1, 2, 4, 8, a.iters, 2 * a.iters}):
         full, small = time_launch(cus, it, lds, grid), time_launch(cus, it, 16, grid)

@@ -33,7 +33,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from nvidia_terraform_modules_amd import ops  # noqa: E402
-from nvidia_terraform_modules_amd.ops import kernels, reference  # noqa: E402
+from nvidia_terraform_modules_amd.ops import reference  # noqa: E402
+from nvidia_terraform_modules_amd.ops.gpu import hbm_pattern, host_link  # noqa: E402
 
 BIN = ROOT / "validation" / "build" / "amdgpu-validate"
 BLOCKS = (16, 32, 64, 128, 256, 512, 1024, 2048)
@@ -84,14 +85,14 @@ def main():
     n = a.mib << 20
     host = torch.empty(n // 4, dtype=torch.int32, pin_memory=True)
     dbuf = torch.empty(n // 4, dtype=torch.int32, device="cuda")
-    res = kernels.new_pattern_result("cuda")
+    res = hbm_pattern.new_pattern_result("cuda")
     ops.host_link_push(host, 1, seed=SEED)
     torch.cuda.synchronize()
 
     # ---- the sweep: every candidate once per round, in one fixed order
     cands = {}
     for nt in (1, 0):
-        for u in kernels.HOST_LINK_UNROLLS:
+        for u in host_link.HOST_LINK_UNROLLS:
             for b in BLOCKS:
                 cfg, tag = (u, nt), f"b{b}_u{u}_{'nt' if nt else 'plain'}"
                 cands["push_" + tag] = lambda b=b, cfg=cfg: ops.host_link_push(
@@ -108,7 +109,7 @@ def main():
     for _ in range(a.rounds):
         for k, fn in cands.items():
             gbps[k].append(n / (event_ms(fn) * 1e-3) / 1e9)
-    bad = kernels.read_pattern_result(res)
+    bad = hbm_pattern.read_pattern_result(res)
     med = {k: statistics.median(v) for k, v in gbps.items()}
     report = {"mib": a.mib, "rounds": a.rounds, "device": torch.cuda.get_device_name(0),
               "pull_bad_words_over_the_sweep": bad.bad_words,
@@ -121,7 +122,7 @@ def main():
             f"spread {max(ref) - min(ref):.2f})")
         for nt in ("nt", "plain"):
             say(f"  {nt:5s}  blocks " + " ".join(f"{b:7d}" for b in BLOCKS))
-            for u in kernels.HOST_LINK_UNROLLS:
+            for u in host_link.HOST_LINK_UNROLLS:
                 say(f"         U={u}    " + " ".join(f"{med[f'{d}_b{b}_u{u}_{nt}']:7.2f}" for b in BLOCKS))
         best = max((k for k in med if k.startswith(d + "_b")), key=med.get)
         say(f"  best {best} {med[best]:.2f} = {med[best] / med[d + '_memcpy']:.3f} of hipMemcpyAsync")
@@ -149,7 +150,7 @@ def main():
         duplex()
         torch.cuda.synchronize()
         shipped["duplex"].append(2 * half / (time.perf_counter() - t0) / 1e9)
-    bad = kernels.read_pattern_result(res)
+    bad = hbm_pattern.read_pattern_result(res)
     table = reference.host_link_chase_table(1024, SEED)
     slots = torch.from_numpy(table.view(np.int64).reshape(-1).copy()).pin_memory()
     want, _ = reference.host_link_chase(slots, 4096)
