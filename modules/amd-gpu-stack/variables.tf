@@ -387,6 +387,12 @@ variable "validation_wave_check" {
   description = "Run the Job's wave data-path and special-function check (K12): on every CU the DPP modifiers, ds_bpermute / ds_permute, ds_swizzle, the permlane16 / permlane32 swaps and v_readlane / v_readfirstlane on hashed words, the gfx950 transposed LDS reads (16-, 8-, 4- and 6-bit), v_bitop3_b32 over all 256 truth tables and v_cvt_pk_bf16_f32, each compared bitwise with a reference kernel that uses none of those instructions, and the fp32 transcendentals (exp, log, rcp, rsq, sqrt, sin, cos), whose results must agree across all workgroups and are measured against brackets the host computes in long double. A wrong word fails the Job by XCD, SE, SH, CU, SIMD, family, op and lane. It sets NTM_WAVE_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/wave/README.md."
 }
 
+variable "validation_attn_check" {
+  type        = bool
+  default     = false
+  description = "Run the Job's fused attention check (K13): a hand-written gfx950 flash-attention forward (bf16, head dimension 128, grouped-query, causal and not) that chains an MFMA into a row reduction, v_exp_f32, a bf16 pack and a second MFMA. Integer-valued inputs make O, the row maxima and the row sums equal a reference kernel without matrix or cross-lane instructions bitwise, repeated until every CU has run a tile; uniform inputs must stay within 2^-7 a + 2^-20 of the reference; the rate of a causal 4 x 32 x 4096 x 4096 pass is reported. A wrong word fails the Job by sub-test, batch, head, row, column and the XCD, SE, SH and CU that computed it. It sets NTM_ATTN_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/attn/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

@@ -187,6 +187,15 @@ SIGNATURES = {
                              ctypes.c_uint, c_vp], c_int),
     "ntm_wave_valu": ([c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_size, c_vp], c_int),
     "ntm_wave_sweep": ([c_int, c_vp, c_size, c_vp, c_vp, c_vp, c_int, ctypes.c_uint, ctypes.c_uint, c_vp], c_int),
+    "ntm_attn_shape_ok": ([c_int, c_int, c_int, c_int, c_int, c_int], c_int),
+    "ntm_attn_table_bytes": ([c_int, c_int, c_int], c_size),
+    "ntm_attn_lds_bytes": ([], c_int),
+    "ntm_attn_fwd": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                      c_vp], c_int),
+    "ntm_attn_reference": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                            c_float, c_vp], c_int),
+    "ntm_attn_compare": ([c_vp, c_vp, c_size, c_vp, c_vp], c_int),
+    "ntm_attn_mismatch_bytes": ([], c_int),
 }
 
 XGMI_SIGNATURES = {

@@ -186,6 +186,15 @@ NTM_API int ntm_wave_sfu_locate(int op, const void* x, unsigned n, unsigned cu_k
 NTM_API int ntm_wave_valu(int reference, int op, const void* a, const void* b, const void* c, void* out, size_t n, void* stream);
 NTM_API int ntm_wave_sweep(int family, const void* in, size_t in_words, const unsigned* layout, const void* expected, void* records, int grid, unsigned fault_wg, unsigned fault_index, void* stream);
 
+/* ---- K13 fused attention forward (ntm/attn.hpp, ntm/attn_plan.hpp) */
+NTM_API int ntm_attn_shape_ok(int B, int Hq, int Hkv, int Sq, int Sk, int causal);
+NTM_API size_t ntm_attn_table_bytes(int B, int Hq, int Sq);
+NTM_API int ntm_attn_lds_bytes(void);
+NTM_API int ntm_attn_fwd(const void* Q, const void* K, const void* V, void* O, float* m, float* l, unsigned* table, int B, int Hq, int Hkv, int Sq, int Sk, int causal, float scale_log2, void* stream);
+NTM_API int ntm_attn_reference(const void* Q, const void* K, const void* V, void* O, float* O32, float* absum, float* m, float* l, int B, int Hq, int Hkv, int Sq, int Sk, int causal, float scale_log2, void* stream);
+NTM_API int ntm_attn_compare(const void* expected, const void* got, size_t n, void* out, void* stream);
+NTM_API int ntm_attn_mismatch_bytes(void);
+
 /* ---- C2 hand-written xGMI all-reduce (xgmi_allreduce.hip, ntm/xgmi_allreduce.hpp)
  * and the allocation / HIP IPC helpers its Python side needs */
 NTM_API int ntm_xgmi_allreduce_bf16(const void* const* in_ptrs, void* const* out_ptrs, unsigned* const* sig_ptrs, int nranks, int rank_base, int nranks_here, int nblk, size_t count, unsigned epoch, unsigned* err, int one_shot, void* stream);

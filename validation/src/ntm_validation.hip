@@ -15,6 +15,7 @@
 // The non-default K1 builds, schedule knobs and diagnostics live in
 // ntm_experimental.hip -> libntm_experimental.so (tests and tools only).
 #include "ntm/atomics.hpp"
+#include "ntm/attn.hpp"
 #include "ntm/aux_kernels.hpp"
 #include "ntm/cu_sweep.hpp"
 #include "ntm/gemm_bf16_pp2.hpp"
@@ -1268,3 +1269,34 @@ NTM_API int ntm_wave_sweep(int family, const void* in, size_t in_words, const un
                            void* records, int grid, unsigned fault_wg, unsigned fault_index, void* stream) {
   return (int)ntm::wave::launch_sweep(family, in, in_words, layout, expected, records, grid, fault_wg, fault_index, S(stream));
 }
+
+// K13: fused attention forward (attn.hpp; shapes, the arithmetic contract, exact inputs and
+// messages in attn_plan.hpp). Q [B][Hq][Sq][128], K and V [B][Hkv][Sk][128], O like Q, all
+// contiguous bf16 and 16-byte aligned; m, l [B][Hq][Sq] fp32 and table (ntm_attn_table_bytes:
+// raw HW_ID and XCC_ID per workgroup) may be null. ntm_attn_reference is the kernel without
+// matrix or cross-lane instructions; each of its outputs may be null: O (bf16), O32 (the fp32
+// quotient before the pack), absum (sum p |v| / l), m, l. ntm_attn_compare counts the 4-byte
+// words that differ into a K7 mismatch record. A bad shape (Hq % Hkv, Sk > 65536, causal with
+// Sk < Sq), a scale that is not positive, a null or misaligned pointer return
+// hipErrorInvalidValue and launch nothing.
+NTM_API int ntm_attn_shape_ok(int B, int Hq, int Hkv, int Sq, int Sk, int causal) {
+  return ntm::attn::shape_ok(B, Hq, Hkv, Sq, Sk, causal) ? 1 : 0;
+}
+NTM_API size_t ntm_attn_table_bytes(int B, int Hq, int Sq) {
+  return B > 0 && Hq > 0 && Sq > 0 ? (size_t)ntm::attn::grid(B, Hq, Sq) * ntm::attn::kTableWords * 4 : 0;
+}
+NTM_API int ntm_attn_lds_bytes() { return ntm::attn::kLdsBytes; }
+NTM_API int ntm_attn_fwd(const void* Q, const void* K, const void* V, void* O, float* m, float* l, unsigned* table, int B,
+                         int Hq, int Hkv, int Sq, int Sk, int causal, float scale_log2, void* stream) {
+  return (int)ntm::attn::launch_attn_fwd(Q, K, V, O, m, l, table, B, Hq, Hkv, Sq, Sk, causal, scale_log2, S(stream));
+}
+NTM_API int ntm_attn_reference(const void* Q, const void* K, const void* V, void* O, float* O32, float* absum, float* m,
+                               float* l, int B, int Hq, int Hkv, int Sq, int Sk, int causal, float scale_log2,
+                               void* stream) {
+  return (int)ntm::attn::launch_attn_reference(Q, K, V, O, O32, absum, m, l, B, Hq, Hkv, Sq, Sk, causal, scale_log2,
+                                               S(stream));
+}
+NTM_API int ntm_attn_compare(const void* expected, const void* got, size_t n, void* out, void* stream) {
+  return (int)ntm::attn::launch_attn_compare(expected, got, n, out, S(stream));
+}
+NTM_API int ntm_attn_mismatch_bytes() { return (int)sizeof(ntm::mx::Mismatch); }

@@ -271,6 +271,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   if (o.mcore_check && !run_mcore(g, r.mcore)) return false;
   if (o.mxq_check && !run_mxq(g, r.mxq)) return false;
   if (o.wave_check && !run_wave(g, r.wave)) return false;
+  if (o.attn_check && !run_attn(g, r.attn)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));

@@ -30,6 +30,10 @@
 //   K12 wave data paths (DPP, permutes, swizzle, lane swaps, transposed LDS
 //       reads), the special-function unit and the gfx950 VALU additions, per
 //       CU, off by default (env NTM_WAVE_CHECK=1; ntm/wave_paths.hpp)    wave.cpp
+//   K13 fused attention forward (MFMA, row reduction, v_exp_f32, bf16 pack, second
+//       MFMA in one loop): exact inputs bitwise against a reference kernel, dense
+//       inputs within a derived tolerance, a rate, off by default
+//       (env NTM_ATTN_CHECK=1; ntm/attn.hpp)                             attn.cpp
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)                                 collectives.hip
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL  collectives.hip
@@ -92,6 +96,12 @@ int main(int argc, char** argv) {
   if (const char* a = std::getenv("NTM_WAVE_CHECK")) o.wave_check = std::string(a) == "1";
   if ((o.fault == "corrupt_wave" || o.fault == "corrupt_wave_sfu") && !o.wave_check) {
     std::fprintf(stderr, "fault-inject %s needs NTM_WAVE_CHECK=1\n", o.fault.c_str());
+    usage();
+    return 2;
+  }
+  if (const char* a = std::getenv("NTM_ATTN_CHECK")) o.attn_check = std::string(a) == "1";
+  if (o.fault == "corrupt_attn" && !o.attn_check) {
+    std::fprintf(stderr, "fault-inject corrupt_attn needs NTM_ATTN_CHECK=1\n");
     usage();
     return 2;
   }

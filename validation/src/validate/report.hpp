@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ntm/atomics_plan.hpp"
+#include "ntm/attn_plan.hpp"
 #include "ntm/cu_sweep_plan.hpp"
 #include "ntm/host_link_plan.hpp"
 #include "ntm/mcore_plan.hpp"
@@ -349,6 +350,26 @@ struct WaveResult {
   static void prometheus(std::ostream& p, const Gpus& res);
 };
 
+// K13 (only with NTM_ATTN_CHECK=1)
+struct AttnResult {
+  bool ran = false;
+  unsigned long long exact_bad = 0;  // 4-byte words of O, m, l that differ from the reference kernel's
+  unsigned long long dense_bad = 0;  // elements beyond 2^-7 a + 2^-20
+  float dense_worst = 0;             // largest error / a of the dense sub-test
+  uint32_t cus = 0, cus_covered = 0, launches = 0;  // exact launches, and the CUs their tables showed
+  double tflops = 0;                 // B 4, Hq 32, Hkv 8, S 4096, causal; reported only
+  double seconds = 0;
+  std::vector<std::string> failures;  // empty = clean
+  std::string json() const {
+    if (!ran) return "";
+    return ",\"attn_exact_bad\":" + std::to_string(exact_bad) + ",\"attn_dense_bad\":" + std::to_string(dense_bad) +
+           ",\"attn_dense_worst_err_over_a\":" + jnum(dense_worst) + ",\"attn_cus_covered\":" +
+           std::to_string(cus_covered) + ",\"attn_launches\":" + std::to_string(launches) + ",\"attn_tflops\":" +
+           jnum(tflops) + ",\"attn_seconds\":" + jnum(seconds);
+  }
+  static void prometheus(std::ostream& p, const Gpus& res);
+};
+
 struct GpuResult {
   int device = -1;
   std::string name, arch;
@@ -367,6 +388,7 @@ struct GpuResult {
   McoreResult mcore;
   MxqResult mxq;
   WaveResult wave;
+  AttnResult attn;
 };
 
 // ------------------------------------------------------------ per-GPU verdicts
@@ -400,7 +422,8 @@ inline std::vector<std::string> gpu_failures(const GpuResult& r, const Opts& o) 
     out.push_back(d + "HBM " + jnum(r.total_gb) + " GB below " + jnum(o.min_hbm_gb) + " GB");
   if (!r.k2.copy_ok) out.push_back(d + "HBM copy mismatch");
   for (const auto* v : {&r.hbm_test.failures, &r.cu_sweep.failures, &r.host_link.failures, &r.mx.failures,
-                        &r.xcd.failures, &r.atomics.failures, &r.mcore.failures, &r.mxq.failures, &r.wave.failures})
+                        &r.xcd.failures, &r.atomics.failures, &r.mcore.failures, &r.mxq.failures, &r.wave.failures,
+                        &r.attn.failures})
     out.insert(out.end(), v->begin(), v->end());
   if (o.hbm_floor_gbps > 0 && r.k2.copy_gbps < o.hbm_floor_gbps)
     out.push_back(d + "HBM copy " + jnum(r.k2.copy_gbps) + " GB/s below floor");
@@ -651,6 +674,17 @@ inline void WaveResult::prometheus(std::ostream& p, const Gpus& res) {
         [](const GpuResult& r) { return r.wave.ran; }, [](const GpuResult& r) { return jnum(r.wave.seconds); });
 }
 
+inline void AttnResult::prometheus(std::ostream& p, const Gpus& res) {
+  auto ran = [](const GpuResult& r) { return r.attn.ran; };
+  gauge(p, res, "amdgpu_validate_attn_bad",
+        "Results of the fused attention check that differ from the reference kernel or lie beyond the tolerance.", ran,
+        [](const GpuResult& r) { return r.attn.exact_bad + r.attn.dense_bad; });
+  gauge(p, res, "amdgpu_validate_attn_tflops", "TFLOP/s of the causal 4 x 32 x 4096 x 4096 attention (reported only).", ran,
+        [](const GpuResult& r) { return jnum(r.attn.tflops); });
+  gauge(p, res, "amdgpu_validate_attn_seconds", "Seconds the fused attention check took.", ran,
+        [](const GpuResult& r) { return jnum(r.attn.seconds); });
+}
+
 // node-exporter textfile-collector format (--prom-out) and Pushgateway body
 // (--pushgateway); labels carry the device index.
 inline std::string prometheus_text(const Report& R) {
@@ -680,6 +714,7 @@ inline std::string prometheus_text(const Report& R) {
   if (o.mcore_check) McoreResult::prometheus(p, R.gpus);
   if (o.mxq_check) MxqResult::prometheus(p, R.gpus);
   if (o.wave_check) WaveResult::prometheus(p, R.gpus);
+  if (o.attn_check) AttnResult::prometheus(p, R.gpus);
   if (!R.rccl_rows.empty() || !R.xgmi_rows.empty())
     p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
       << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(Report::peak_any(R.rccl_rows)) << "\n"
@@ -710,7 +745,8 @@ inline std::string report_json(const Report& R) {
     js += (i ? "," : "") + std::string("{\"device\":") + std::to_string(r.device) +
           ",\"name\":" + jstr(r.name) + ",\"arch\":" + jstr(r.arch) + ",\"hbm_total_gb\":" + jnum(r.total_gb) +
           r.k1.json() + r.fp8.json() + r.sk.json() + r.k2.json() + r.hbm_test.json() + r.cu_sweep.json() +
-          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + r.mxq.json() + r.wave.json() + "}";
+          r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + r.mxq.json() + r.wave.json() +
+          r.attn.json() + "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(R.rccl_rows);
   js += ",\"xgmi_allreduce_bf16\":" + coll_json(R.xgmi_rows);
