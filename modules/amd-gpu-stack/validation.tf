@@ -71,7 +71,7 @@ locals {
     NCCL_IB_DISABLE        = "1"
     NCCL_SOCKET_IFNAME     = "lo"
     HSA_NO_SCRATCH_RECLAIM = "1"
-  }, var.validation_atomics_check ? { NTM_ATOMICS_CHECK = "1" } : {}, var.validation_mcore_check ? { NTM_MCORE_CHECK = "1" } : {}, var.validation_mxq_check ? { NTM_MXQ_CHECK = "1" } : {}, var.validation_wave_check ? { NTM_WAVE_CHECK = "1" } : {}, var.validation_attn_check ? { NTM_ATTN_CHECK = "1" } : {}, var.validation_env)
+  }, var.validation_atomics_check ? { NTM_ATOMICS_CHECK = "1" } : {}, var.validation_mcore_check ? { NTM_MCORE_CHECK = "1" } : {}, var.validation_mxq_check ? { NTM_MXQ_CHECK = "1" } : {}, var.validation_wave_check ? { NTM_WAVE_CHECK = "1" } : {}, var.validation_attn_check ? { NTM_ATTN_CHECK = "1" } : {}, var.validation_pda_check ? { NTM_PDA_CHECK = "1" } : {}, var.validation_env)
 }
 
 resource "kubernetes_job_v1" "gpu_validation" {

@@ -393,6 +393,12 @@ variable "validation_attn_check" {
   description = "Run the Job's fused attention check (K13): a hand-written gfx950 flash-attention forward (bf16, head dimension 128, grouped-query, causal and not) that chains an MFMA into a row reduction, v_exp_f32, a bf16 pack and a second MFMA. Integer-valued inputs make O, the row maxima and the row sums equal a reference kernel without matrix or cross-lane instructions bitwise, repeated until every CU has run a tile; uniform inputs must stay within 2^-7 a + 2^-20 of the reference; the rate of a causal 4 x 32 x 4096 x 4096 pass is reported. A wrong word fails the Job by sub-test, batch, head, row, column and the XCD, SE, SH and CU that computed it. It sets NTM_ATTN_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/attn/README.md."
 }
 
+variable "validation_pda_check" {
+  type        = bool
+  default     = false
+  description = "Run the Job's paged-KV decode attention check (K14): a hand-written gfx950 decode attention (bf16, head dimension 128, grouped-query, 1 to 4 new tokens per sequence) that reaches its keys through a block table in 16-token pages, cuts them over several workgroups per sequence (split-KV) and merges the partial softmax state afterwards. Integer-valued inputs in a shuffled pool with shared prefixes, a NaN poison page and NaN page tails make O, the row maxima and the row sums equal K13's reference kernel on the gathered keys bitwise, repeated until every CU has run a split; uniform inputs must stay within 2^-7 a + 2^-20 of the reference; the K and V read rate of 32 sequences of 8192 keys (1 GiB together, past the Infinity Cache) is reported. A wrong word fails the Job by sub-test, sequence, head, token, column and the XCD, SE, SH and CU of the row's split workgroups. It sets NTM_PDA_CHECK=1 in the Job's environment (the binary has no flag for it yet); the default false leaves the Job unchanged. Measurements: profiles/pda/README.md."
+}
+
 variable "validation_allreduce_max_mib" {
   type        = number
   default     = 1024

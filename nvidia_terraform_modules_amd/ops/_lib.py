@@ -196,6 +196,13 @@ SIGNATURES = {
                             c_float, c_vp], c_int),
     "ntm_attn_compare": ([c_vp, c_vp, c_size, c_vp, c_vp], c_int),
     "ntm_attn_mismatch_bytes": ([], c_int),
+    "ntm_pda_shape_ok": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int], c_int),
+    "ntm_pda_workspace_bytes": ([c_int, c_int, c_int], c_size),
+    "ntm_pda_table_bytes": ([c_int, c_int, c_int], c_size),
+    "ntm_pda_lds_bytes": ([], c_int),
+    "ntm_pda_default_splits": ([c_int, c_int, c_int, c_int], c_int),
+    "ntm_pda_fwd": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                     c_int, c_int, c_float, c_vp], c_int),
 }
 
 XGMI_SIGNATURES = {

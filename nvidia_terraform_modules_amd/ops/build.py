@@ -41,7 +41,7 @@ SHIPPING_SRCS = ("ntm_validation.hip", "xgmi_allreduce.hip")
 BINARY_SRCS = ("validate/main.cpp", "validate/host.cpp", "validate/gpu.cpp", "validate/hbm_test.cpp",
                "validate/cu_sweep.cpp", "validate/host_link.cpp", "validate/mx_check.cpp",
                "validate/xcd_sweep.cpp", "validate/atomics.cpp", "validate/mcore.cpp", "validate/mxq.cpp",
-               "validate/wave.cpp", "validate/attn.cpp",
+               "validate/wave.cpp", "validate/attn.cpp", "validate/pda.cpp",
                "validate/collectives.hip")
 BIN_NAME = "amdgpu-validate"
 

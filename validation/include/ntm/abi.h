@@ -195,6 +195,14 @@ NTM_API int ntm_attn_reference(const void* Q, const void* K, const void* V, void
 NTM_API int ntm_attn_compare(const void* expected, const void* got, size_t n, void* out, void* stream);
 NTM_API int ntm_attn_mismatch_bytes(void);
 
+/* ---- K14 paged-KV decode attention (ntm/pda.hpp, ntm/pda_plan.hpp) */
+NTM_API int ntm_pda_shape_ok(int B, int Hq, int Hkv, int T, int max_pages, int pages, int splits);
+NTM_API size_t ntm_pda_workspace_bytes(int B, int Hkv, int splits);
+NTM_API size_t ntm_pda_table_bytes(int B, int Hkv, int splits);
+NTM_API int ntm_pda_lds_bytes(void);
+NTM_API int ntm_pda_default_splits(int B, int Hkv, int max_len, int cus);
+NTM_API int ntm_pda_fwd(const void* Q, const void* Kpool, const void* Vpool, const int* block_table, const int* seq_lens, void* O, float* m, float* l, void* workspace, unsigned* table, int B, int Hq, int Hkv, int T, int max_pages, int pages, int splits, float scale_log2, void* stream);
+
 /* ---- C2 hand-written xGMI all-reduce (xgmi_allreduce.hip, ntm/xgmi_allreduce.hpp)
  * and the allocation / HIP IPC helpers its Python side needs */
 NTM_API int ntm_xgmi_allreduce_bf16(const void* const* in_ptrs, void* const* out_ptrs, unsigned* const* sig_ptrs, int nranks, int rank_base, int nranks_here, int nblk, size_t count, unsigned epoch, unsigned* err, int one_shot, void* stream);

@@ -32,6 +32,7 @@
 #include "ntm/mcore.hpp"
 #include "ntm/mx_gemm.hpp"
 #include "ntm/mxq.hpp"
+#include "ntm/pda.hpp"
 #include "ntm/wave_paths.hpp"
 #include "ntm/xcd_sweep.hpp"
 
@@ -1300,3 +1301,26 @@ NTM_API int ntm_attn_compare(const void* expected, const void* got, size_t n, vo
   return (int)ntm::attn::launch_attn_compare(expected, got, n, out, S(stream));
 }
 NTM_API int ntm_attn_mismatch_bytes() { return (int)sizeof(ntm::mx::Mismatch); }
+
+// K14: paged-KV decode attention (pda.hpp; shapes, the split plan and the arithmetic contract in
+// pda_plan.hpp). Q and O [B][Hq][T][128], the K and V pools [pages][Hkv][16][128], all contiguous
+// bf16 and 16-byte aligned; block_table [B][max_pages] and seq_lens [B] int32 on the device;
+// workspace of ntm_pda_workspace_bytes, 16-byte aligned; m, l [B][Hq][T] fp32 and table
+// (ntm_pda_table_bytes: raw HW_ID and XCC_ID per split workgroup) may be null. Two launches on
+// the stream: the split kernel, then the combine. A bad shape (Hq % Hkv, T > 4, Hq / Hkv * T > 32,
+// splits outside 1 .. 64, max_pages > 4096), a scale that is not positive, a null or misaligned
+// pointer return hipErrorInvalidValue and launch nothing. The reference is ntm_attn_reference on
+// the gathered keys of one sequence, the compare ntm_attn_compare.
+NTM_API int ntm_pda_shape_ok(int B, int Hq, int Hkv, int T, int max_pages, int pages, int splits) {
+  return ntm::pda::shape_ok(B, Hq, Hkv, T, max_pages, pages, splits) ? 1 : 0;
+}
+NTM_API size_t ntm_pda_workspace_bytes(int B, int Hkv, int splits) { return ntm::pda::workspace_bytes(B, Hkv, splits); }
+NTM_API size_t ntm_pda_table_bytes(int B, int Hkv, int splits) { return ntm::pda::table_bytes(B, Hkv, splits); }
+NTM_API int ntm_pda_lds_bytes() { return ntm::pda::kLdsBytes; }
+NTM_API int ntm_pda_default_splits(int B, int Hkv, int max_len, int cus) { return ntm::pda::pda_splits(B, Hkv, max_len, cus); }
+NTM_API int ntm_pda_fwd(const void* Q, const void* Kpool, const void* Vpool, const int* block_table, const int* seq_lens,
+                        void* O, float* m, float* l, void* workspace, unsigned* table, int B, int Hq, int Hkv, int T,
+                        int max_pages, int pages, int splits, float scale_log2, void* stream) {
+  return (int)ntm::pda::launch_pda_fwd(Q, Kpool, Vpool, block_table, seq_lens, O, m, l, workspace, table, B, Hq, Hkv, T,
+                                       max_pages, pages, splits, scale_log2, S(stream));
+}

@@ -113,6 +113,7 @@ bool run_mcore(const GpuCtx& g, McoreResult& r);         // K10, mcore.cpp
 bool run_mxq(const GpuCtx& g, MxqResult& r);             // K11, mxq.cpp
 bool run_wave(const GpuCtx& g, WaveResult& r);           // K12, wave.cpp
 bool run_attn(const GpuCtx& g, AttnResult& r);           // K13, attn.cpp
+bool run_pda(const GpuCtx& g, PdaResult& r);             // K14, pda.cpp
 
 // K1 / K2 and the calls of the above on one GPU (gpu.cpp)
 bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r);

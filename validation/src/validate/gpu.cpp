@@ -272,6 +272,7 @@ bool run_gpu(int dev, bool last, const Opts& o, GpuResult& r) {
   if (o.mxq_check && !run_mxq(g, r.mxq)) return false;
   if (o.wave_check && !run_wave(g, r.wave)) return false;
   if (o.attn_check && !run_attn(g, r.attn)) return false;
+  if (o.pda_check && !run_pda(g, r.pda)) return false;
   CK(hipEventDestroy(e0));
   CK(hipEventDestroy(e1));
   CK(hipStreamDestroy(s));

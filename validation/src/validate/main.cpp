@@ -34,6 +34,10 @@
 //       MFMA in one loop): exact inputs bitwise against a reference kernel, dense
 //       inputs within a derived tolerance, a rate, off by default
 //       (env NTM_ATTN_CHECK=1; ntm/attn.hpp)                             attn.cpp
+//   K14 paged-KV decode attention (block-table gather, split-KV, merge of partial
+//       softmax state): exact inputs bitwise against K13's reference kernel on the
+//       gathered keys, dense inputs within the derived tolerance, a KV read rate,
+//       off by default (env NTM_PDA_CHECK=1; ntm/pda.hpp)                pda.cpp
 //   C1  RCCL all-reduce sweep over xGMI (ncclCommInitAll, one process owns
 //       all GPUs; every element checked)                                 collectives.hip
 //   C2  hand-written two-shot all-reduce over peer-mapped xGMI, vs RCCL  collectives.hip
@@ -102,6 +106,12 @@ int main(int argc, char** argv) {
   if (const char* a = std::getenv("NTM_ATTN_CHECK")) o.attn_check = std::string(a) == "1";
   if (o.fault == "corrupt_attn" && !o.attn_check) {
     std::fprintf(stderr, "fault-inject corrupt_attn needs NTM_ATTN_CHECK=1\n");
+    usage();
+    return 2;
+  }
+  if (const char* a = std::getenv("NTM_PDA_CHECK")) o.pda_check = std::string(a) == "1";
+  if (o.fault == "corrupt_pda" && !o.pda_check) {
+    std::fprintf(stderr, "fault-inject corrupt_pda needs NTM_PDA_CHECK=1\n");
     usage();
     return 2;
   }

@@ -42,6 +42,7 @@ struct Opts {
   bool mxq_check = false;       // K11: env NTM_MXQ_CHECK=1 (no flag yet: validate/README.md)
   bool wave_check = false;      // K12: env NTM_WAVE_CHECK=1 (no flag yet: validate/README.md)
   bool attn_check = false;      // K13: env NTM_ATTN_CHECK=1 (no flag yet: validate/README.md)
+  bool pda_check = false;       // K14: env NTM_PDA_CHECK=1 (no flag yet: validate/README.md)
   double xcd_ratio = 0;         // fail an XCD below ratio x its card's median; 0 = report only
   long allreduce_max_mib = 8192;  // 8 GiB, capped by free HBM
   bool xgmi = true;

@@ -24,6 +24,7 @@
 #include "ntm/host_link_plan.hpp"
 #include "ntm/mcore_plan.hpp"
 #include "ntm/mxq_plan.hpp"
+#include "ntm/pda_plan.hpp"
 #include "ntm/wave_paths_plan.hpp"
 #include "ntm/xcd_sweep_plan.hpp"
 
@@ -370,6 +371,27 @@ struct AttnResult {
   static void prometheus(std::ostream& p, const Gpus& res);
 };
 
+// K14 (only with NTM_PDA_CHECK=1)
+struct PdaResult {
+  bool ran = false;
+  unsigned long long exact_bad = 0;  // 4-byte words of O, m, l that differ from the reference kernel's
+  unsigned long long dense_bad = 0;  // elements beyond 2^-7 a + 2^-20
+  float dense_worst = 0;             // largest error / a of the dense sub-test
+  uint32_t cus = 0, cus_covered = 0, launches = 0;  // exact launches, and the CUs their tables showed
+  uint32_t splits = 0;               // the default S of the timed shape on this device
+  double kv_gbps = 0;                // B 32, Hq 32, Hkv 8, T 1, len 8192: K and V bytes / time; reported only
+  double seconds = 0;
+  std::vector<std::string> failures;  // empty = clean
+  std::string json() const {
+    if (!ran) return "";
+    return ",\"pda_exact_bad\":" + std::to_string(exact_bad) + ",\"pda_dense_bad\":" + std::to_string(dense_bad) +
+           ",\"pda_dense_worst_err_over_a\":" + jnum(dense_worst) + ",\"pda_cus_covered\":" +
+           std::to_string(cus_covered) + ",\"pda_launches\":" + std::to_string(launches) + ",\"pda_splits\":" +
+           std::to_string(splits) + ",\"pda_kv_gbps\":" + jnum(kv_gbps) + ",\"pda_seconds\":" + jnum(seconds);
+  }
+  static void prometheus(std::ostream& p, const Gpus& res);
+};
+
 struct GpuResult {
   int device = -1;
   std::string name, arch;
@@ -389,6 +411,7 @@ struct GpuResult {
   MxqResult mxq;
   WaveResult wave;
   AttnResult attn;
+  PdaResult pda;
 };
 
 // ------------------------------------------------------------ per-GPU verdicts
@@ -423,7 +446,7 @@ inline std::vector<std::string> gpu_failures(const GpuResult& r, const Opts& o) 
   if (!r.k2.copy_ok) out.push_back(d + "HBM copy mismatch");
   for (const auto* v : {&r.hbm_test.failures, &r.cu_sweep.failures, &r.host_link.failures, &r.mx.failures,
                         &r.xcd.failures, &r.atomics.failures, &r.mcore.failures, &r.mxq.failures, &r.wave.failures,
-                        &r.attn.failures})
+                        &r.attn.failures, &r.pda.failures})
     out.insert(out.end(), v->begin(), v->end());
   if (o.hbm_floor_gbps > 0 && r.k2.copy_gbps < o.hbm_floor_gbps)
     out.push_back(d + "HBM copy " + jnum(r.k2.copy_gbps) + " GB/s below floor");
@@ -685,6 +708,17 @@ inline void AttnResult::prometheus(std::ostream& p, const Gpus& res) {
         [](const GpuResult& r) { return jnum(r.attn.seconds); });
 }
 
+inline void PdaResult::prometheus(std::ostream& p, const Gpus& res) {
+  auto ran = [](const GpuResult& r) { return r.pda.ran; };
+  gauge(p, res, "amdgpu_validate_pda_bad",
+        "Results of the paged-KV decode attention check that differ from the reference kernel or lie beyond the tolerance.",
+        ran, [](const GpuResult& r) { return r.pda.exact_bad + r.pda.dense_bad; });
+  gauge(p, res, "amdgpu_validate_pda_kv_gbps", "GB/s of K and V read by the 32 x 8192-key paged decode pass (reported only).",
+        ran, [](const GpuResult& r) { return jnum(r.pda.kv_gbps); });
+  gauge(p, res, "amdgpu_validate_pda_seconds", "Seconds the paged-KV decode attention check took.", ran,
+        [](const GpuResult& r) { return jnum(r.pda.seconds); });
+}
+
 // node-exporter textfile-collector format (--prom-out) and Pushgateway body
 // (--pushgateway); labels carry the device index.
 inline std::string prometheus_text(const Report& R) {
@@ -715,6 +749,7 @@ inline std::string prometheus_text(const Report& R) {
   if (o.mxq_check) MxqResult::prometheus(p, R.gpus);
   if (o.wave_check) WaveResult::prometheus(p, R.gpus);
   if (o.attn_check) AttnResult::prometheus(p, R.gpus);
+  if (o.pda_check) PdaResult::prometheus(p, R.gpus);
   if (!R.rccl_rows.empty() || !R.xgmi_rows.empty())
     p << "# TYPE amdgpu_validate_allreduce_busbw_gbps gauge\n"
       << "amdgpu_validate_allreduce_busbw_gbps{impl=\"rccl\"} " << jnum(Report::peak_any(R.rccl_rows)) << "\n"
@@ -746,7 +781,7 @@ inline std::string report_json(const Report& R) {
           ",\"name\":" + jstr(r.name) + ",\"arch\":" + jstr(r.arch) + ",\"hbm_total_gb\":" + jnum(r.total_gb) +
           r.k1.json() + r.fp8.json() + r.sk.json() + r.k2.json() + r.hbm_test.json() + r.cu_sweep.json() +
           r.host_link.json() + r.mx.json() + r.xcd.json() + r.atomics.json() + r.mcore.json() + r.mxq.json() + r.wave.json() +
-          r.attn.json() + "}";
+          r.attn.json() + r.pda.json() + "}";
   }
   js += "],\"rccl_allreduce\":" + coll_json(R.rccl_rows);
   js += ",\"xgmi_allreduce_bf16\":" + coll_json(R.xgmi_rows);
